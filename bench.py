@@ -25,11 +25,26 @@ touches the GPU) and exits with their status; under torchrun (WORLD_SIZE set)
 it is one rank.  Rank 0 prints ONE JSON line: `value` = decoded bytes of all
 ranks x steps / the max-over-ranks time of the timed steps.
 
-Beside the line (rank 0, N = 1): `cpu_baseline` — the reference library
-(oracle/_ref: /root/reference/src compiled against liblz4 1.9.3 / libzstd
-1.4.9) on the host cores, 1 thread and every usable core; `end_to_end` — the
-drop-in zseek_pread into host memory (PCIe-inclusive, never `value`);
-`latency_4k_us` — 4 KiB random zseek_pread requests, ours and the reference's.
+A plain run does only what `value` needs: input, upload, warm-up, the timed
+steps, the line.  Everything else is behind `--full` (its fields are null
+without it): the bit-exact check against the generator, the per-stage kernel
+times (`roofline.stages` / `kernel` / `dominant_kernel` / `traffic`), the
+RCCL reassembly, `--codec lz4c`'s `launch_by_frames` / `writer_end_to_end`,
+and beside the line (rank 0, N = 1): `cpu_baseline` — the reference library
+(oracle/_ref: the reference sources compiled out of tree against liblz4 1.9.3
+/ libzstd 1.4.9) on the host cores, 1 thread and every usable core;
+`end_to_end` — the drop-in zseek_pread into host memory (PCIe-inclusive, never
+`value`); `latency_4k_us` — 4 KiB random zseek_pread requests, ours and the
+reference's.  The --no-* switches and --profile trim a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left in the caller's
+buffers (rank 0's, right after the timed region) as DIR/<name>.npy: `status`
+(every frame's status word), `frame_byte_sums` (float64 sum of each frame's
+decoded bytes: every output byte counts) and `decoded_sample` (the decoded
+bytes at a fixed, seeded set of positions); `--codec lz4c`: `csize`,
+`frame_byte_sums` and `compressed_sample` of the frames written.  The input is
+generated, never random, so two builds given the same arguments are
+comparable file by file.
 """
 from __future__ import annotations
 
@@ -93,6 +108,12 @@ def parse(argv=None):
     p.add_argument("--no-latency", action="store_true")
     p.add_argument("--no-verify", action="store_true")
     p.add_argument("--reassemble", type=int, default=-1, help="1/0; default on when N > 1")
+    p.add_argument("--full", action="store_true",
+                   help="also verify the output, time the stages, reassemble (N > 1) and run the "
+                        "legs beside the line (CPU baseline, end to end, latency); off: only "
+                        "what `value` needs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     p.add_argument("--profile", action="store_true", help="few steps, no extras (rocprof runs)")
     p.add_argument("--codec", choices=["lz4", "zstd", "lz4c"], default="lz4",
                    help="lz4 = configs 2-4 (the headline metric); zstd = config 5; lz4c = "
@@ -274,6 +295,45 @@ def decode_launches(z, torch, desc_dev, n, comp, out, status, zstd, per):
             raise SystemExit("zsk_lz4_decode_frames launch failed")
 
 
+DUMP_SAMPLE = 1 << 22     # sampled output bytes (16 MB as float32)
+DUMP_SEED = 20240611
+DUMP_GROUP = 64 << 20     # buffer bytes reduced at a time (x8 as int64 prefix sums)
+
+
+def dump_outputs(path, torch, small, buf, offs, sizes, sample_name):
+    """--dump-outputs: `small` tensors whole; of the byte buffer `buf`, whose
+    frame f is buf[offs[f], +sizes[f]) (ascending), every frame's byte sum
+    (float64, exact) and the bytes at DUMP_SAMPLE seeded positions inside the
+    frames (float32).  Bytes between frames are never read into a file."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in small.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    offs, sizes = np.asarray(offs, np.int64), np.asarray(sizes, np.int64)
+    n = len(offs)
+    ends = offs + sizes
+    sums = np.zeros(n, np.float64)
+    f = 0
+    while f < n:
+        g = max(f + 1, int(np.searchsorted(ends, offs[f] + DUMP_GROUP, side="right")))
+        a, b = int(offs[f]), int(ends[f:g].max())
+        pre = torch.zeros(b - a + 1, dtype=torch.int64, device=buf.device)
+        torch.cumsum(buf[a:b], 0, dtype=torch.int64, out=pre[1:])
+        lo = torch.from_numpy(offs[f:g] - a).to(buf.device)
+        hi = torch.from_numpy(ends[f:g] - a).to(buf.device)
+        sums[f:g] = (pre[hi] - pre[lo]).cpu().numpy()
+        f = g
+    np.save(os.path.join(path, "frame_byte_sums.npy"), sums)
+    full = np.flatnonzero(sizes > 0)
+    sample = np.zeros(0, np.float32)
+    if len(full):
+        rng = np.random.default_rng(DUMP_SEED)
+        k = int(min(DUMP_SAMPLE, sizes.sum()))
+        fr = full[rng.integers(0, len(full), k)]
+        pos = np.sort(offs[fr] + (rng.random(k) * sizes[fr]).astype(np.int64))
+        sample = buf[torch.from_numpy(pos).to(buf.device)].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(path, sample_name + ".npy"), sample)
+
+
 # ---------------------------------------------------------------------------
 def main():
     args = parse()
@@ -308,6 +368,9 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
     if args.profile:
         args.no_cpu_baseline = args.no_e2e = args.no_verify = args.no_latency = True
+    if not args.full:   # a plain run: the timed steps and the line, nothing beside them
+        args.no_cpu_baseline = args.no_e2e = args.no_verify = args.no_latency = True
+        args.reassemble = 0
     if args.codec == "lz4c":
         return main_compress(args, torch, dist, z, dev, world, rank)
     zstd = args.codec == "zstd"
@@ -383,11 +446,14 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     t_max = float(t[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, {"status": status},
+                     out, sh.desc["d_off"], sh.desc["d_size"], "decoded_sample")
 
     # per-stage HIP events of the library's launches, from as many launches
     # right after the timed region (untimed: events between kernels cost time)
     stage_ms, n_timed = None, 0
-    if not harness:
+    if args.full and not harness:
         z.kernel_timing(True)
         for _ in range(args.steps):
             step()
@@ -578,6 +644,9 @@ def main_compress(args, torch, dist, z, dev, world, rank):
 
     cs = csize.cpu().numpy().astype(np.int64)
     comp_bytes = int(cs.sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, {"csize": csize},
+                     d_dst, desc["dst_off"], cs, "compressed_sample")
     verified = None
     if not args.no_verify:
         img = np.asarray(z.lz4_seekable(data, args.frame, 0, args.threads))
@@ -595,7 +664,7 @@ def main_compress(args, torch, dist, z, dev, world, rank):
             raise SystemExit("GPU frames differ from liblz4's")
     cpu = by_frames = writer = None
     host_info = host_cpus()
-    if rank == 0 and world == 1 and not args.profile:
+    if rank == 0 and world == 1 and args.full and not args.profile:
         # launch time against frames per launch (a lane compresses one frame
         # serially, so throughput grows with frames in flight)
         by_frames = {}

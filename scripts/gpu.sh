@@ -28,11 +28,13 @@ smoke)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 ;;
 bench)
   tag=$1; shift; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # the whole line: stages, verification, the legs beside it
   timeout -k 10 600 python bench.py "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err \
       || { tail -20 gpurun_out/$tag/bench.err; exit 1; }
   cat gpurun_out/$tag/bench.json ;;
 trace)
   tag=$1; shift; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # --profile trims it to the timed steps + the stage-timing pass, as ever
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$tag/trace \
       -- python bench.py --profile --steps 5 --warmup 1 "$@" > gpurun_out/$tag/trace.log 2>&1 \
       || { tail -20 gpurun_out/$tag/trace.log; exit 1; }
@@ -40,6 +42,7 @@ trace)
 pmc)
   tag=$1; name=$2; c=$3; shift 3; mkdir -p gpurun_out/$tag
   d=gpurun_out/$tag/$name
+  set -- --full "$@"
   timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d $d -- python bench.py --profile --steps 2 --warmup 1 "$@" \
       > $d.log 2>&1 || { tail -5 $d.log; exit 1; } ;;
 evidence)

@@ -95,7 +95,7 @@ def test_bench_spawns_ranks_harness(partition):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
-                        "--harness-check", "--total-size", "8M", "--size", "4M", "--steps", "2",
+                        "--full", "--harness-check", "--total-size", "8M", "--size", "4M", "--steps", "2",
                         "--warmup", "1", "--partition", partition],
                        capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]

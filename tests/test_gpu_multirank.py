@@ -27,7 +27,7 @@ def test_bench_two_ranks_share_gpu(gpu, partition):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["ZSEEK_BENCH_SHARE_GPU"] = "1"
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
                         "--total-size", "512M", "--size", "256M", "--steps", "2", "--warmup", "1",
                         "--partition", partition, "--no-cpu-baseline", "--no-e2e", "--no-latency",
                         "--threads", "8"],
