@@ -117,8 +117,9 @@ ZSEEK_EXPORT int zsk_lz4_decode_frames_ex(const zsk_frame_desc_t *d_desc,
 ZSEEK_EXPORT const char *zsk_lz4_kernel_name(uint32_t nframes);
 
 /* Name of the parse kernel the two-phase decoder runs for a frame of
- * @c_size compressed bytes in a batch of @nframes frames (lz4_lean_kernel,
- * lz4_scan_kernel or lz4_chunk_kernel; lz4_wave_kernel for small batches):
+ * @c_size compressed bytes in a batch of @nframes frames (lz4_lean_pair_kernel,
+ * lz4_lean_kernel on the block route, lz4_scan_kernel or lz4_chunk_kernel;
+ * lz4_wave_kernel for small batches):
  * the library's routing, exposed so tools attribute time and traffic to the
  * kernel that actually runs. */
 ZSEEK_EXPORT const char *zsk_lz4_parse_kernel_name(uint32_t nframes, uint32_t c_size);

@@ -20,7 +20,11 @@
 //   * the ring is filled through a D-deep software pipeline of 32-byte
 //     loads (one slot retired into the ring and one load issued per
 //     sub-step, every sub-step issuing the same vector-memory ops so the
-//     compiler's vmcnt waits retire exactly the slot consumed).
+//     compiler's vmcnt waits retire exactly the slot consumed);
+//   * on the frame route two waves share each 64 frames
+//     (lz4_lean_pair_kernel): one runs only the parse chain, its partner the
+//     ring fill and the item flush; the block route runs everything in one
+//     wave (lz4_lean_kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -266,7 +270,9 @@ __device__ __forceinline__ int32_t hdr_status(Lane &L)
 // Returns true when the lane needs the exact step (a rule failed for a reason
 // other than bytes still in flight, or the lane is in another phase).
 // (fe: the flush-table entry read with the token; the line it names is read
-// with the offset, so the flush adds no LDS round trip of its own)
+// with the offset, so the flush adds no LDS round trip of its own; FV false,
+// the pair kernel's parser wave: no flush read, the mover wave does it)
+template <bool FV = true>
 __device__ __forceinline__ bool fast(Lane &L, uint32_t fe, uint32_t pc, u32x4 &fv)
 {
     const uint32_t ip = L.ip, ph = L.ph;
@@ -277,7 +283,8 @@ __device__ __forceinline__ bool fast(Lane &L, uint32_t fe, uint32_t pc, u32x4 &f
     const uint32_t lit = lext ? 15 + e : tok >> 4;
     const uint32_t p = ip + (lext ? 2 : 1);
     const uint32_t q = p + lit;
-    fv = *lp<u32x4>(fe + 16 * pc);
+    if (FV)
+        fv = *lp<u32x4>(fe + 16 * pc);
     const uint32_t o4q = r4(L, q);
     const uint32_t qq = po ? ip : q;
     const uint32_t o4 = po ? w : o4q;
@@ -557,6 +564,48 @@ __device__ __forceinline__ uint32_t flush_hand(Lane &L, uint32_t tab)
     return min((uint32_t)__builtin_popcountll(rm), kFlush);
 }
 
+// the sub-step's staged item(s) into the lane's buffer (slots k, k + 1 mod 32)
+__device__ __forceinline__ void put_items(Lane &L)
+{
+    const uint32_t ibuf = L.ring + kIBuf;
+    const uint32_t a0 = L.nk ? ibuf + 8 * (L.k & 31) : L.ring + kSink;
+    const uint32_t a1 = L.nk == 2 ? ibuf + 8 * ((L.k + 1) & 31) : L.ring + kSink + 8;
+    *lp<uint64_t>(a0) = ((uint64_t)L.ibw << 32) | L.ia;
+    *lp<uint64_t>(a1) = ((uint64_t)L.ib2 << 32) | L.ia2;
+    L.k += L.nk;
+    L.nk = 0;
+}
+
+// retire slot S into the ring when it holds the stream's next bytes
+__device__ __forceinline__ void fill_retire(Lane &L, const Fill &S)
+{
+    const bool in = S.x == L.avail;
+    ring_put(L, S.x, S.a, S.b, in);
+    ring_put(L, S.x + 32, S.c, S.d, in && S.h2);
+    L.avail = in ? L.avail + (S.h2 ? 64 : 32) : L.avail;
+}
+
+// restart the stream at need_x if that byte was never requested (a long
+// literal run was skipped), then issue S's next loads: 32 bytes if that
+// leaves every byte from need_x on intact, and 32 more if those do too
+__device__ __forceinline__ void fill_issue(Lane &L, Fill &S, uint32_t need_x, bool live)
+{
+    const bool jump = need_x >= L.fill;
+    L.fill = jump ? need_x & ~31u : L.fill;
+    L.avail = jump ? L.fill : L.avail;
+    const uint32_t lim = need_x + kRing - 16;
+    const bool fl = live & (L.fill < L.cx0 + L.clen) & (L.fill + 32 <= lim);
+    const bool f2 = fl & (L.fill + 32 < L.cx0 + L.clen) & (L.fill + 64 <= lim);
+    const uint32_t fx = fl ? L.fill : kOff;
+    S.x = fx;
+    S.h2 = f2;
+    S.a = bload16(L.cin, fx);
+    S.b = bload16(L.cin, fl ? fx + 16 : kOff);
+    S.c = bload16(L.cin, f2 ? fx + 32 : kOff);
+    S.d = bload16(L.cin, f2 ? fx + 48 : kOff);
+    L.fill = fl ? L.fill + (f2 ? 64 : 32) : L.fill;
+}
+
 template <int DIAG>
 __device__ __forceinline__ void flush_store(const Lane &L, uint64_t fe, const u32x4 &fv, uint32_t g,
                                             uint32_t pc, uint32_t fcnt)
@@ -574,12 +623,8 @@ __device__ __forceinline__ void flush_store(const Lane &L, uint64_t fe, const u3
 template <bool SLOW, bool FILL, int DIAG>
 __device__ __forceinline__ void sub(Lane &L, Fill &S, uint32_t lane, uint32_t tab, uint32_t &fcnt)
 {
-    if (FILL) {
-        const bool in = S.x == L.avail;
-        ring_put(L, S.x, S.a, S.b, in);
-        ring_put(L, S.x + 32, S.c, S.d, in && S.h2);
-        L.avail = in ? L.avail + (S.h2 ? 64 : 32) : L.avail;
-    }
+    if (FILL)
+        fill_retire(L, S);
     const uint32_t g = lane >> 3, pc = lane & 7;
     const uint64_t fe = *lp<uint64_t>(tab + 8 * (g < fcnt ? g : kFlush));
     u32x4 fv;
@@ -602,53 +647,78 @@ __device__ __forceinline__ void sub(Lane &L, Fill &S, uint32_t lane, uint32_t ta
         if (need)
             slow(L);
     }
-    // the item(s) into the lane's buffer (slots k, k + 1 mod 32): after the
-    // handed-over line was read
-    auto put_items = [&]() {
-        const uint32_t ibuf = L.ring + kIBuf;
-        const uint32_t a0 = L.nk ? ibuf + 8 * (L.k & 31) : L.ring + kSink;
-        const uint32_t a1 = L.nk == 2 ? ibuf + 8 * ((L.k + 1) & 31) : L.ring + kSink + 8;
-        *lp<uint64_t>(a0) = ((uint64_t)L.ibw << 32) | L.ia;
-        *lp<uint64_t>(a1) = ((uint64_t)L.ib2 << 32) | L.ia2;
-        L.k += L.nk;
-        L.nk = 0;
-    };
-    put_items();
+    // after the handed-over line was read
+    put_items(L);
     if (!(DIAG & 32)) {
         // a second sequence in the same sub-step when its bytes are in the
         // ring: the fill, flush and loop work then serve two (config 2, plan +
         // parse: 1.085 -> 1.032 ms; DIAG 32, tuning: one sequence, as round 3)
         u32x4 dv;
         (void)fast(L, L.ring + kSink, 0, dv);
-        put_items();
+        put_items(L);
     }
     wave_lds_sync();
     fcnt = flush_hand(L, tab);
     wave_lds_sync();
     if (!FILL)
         return;
-    // the next byte needed was never requested (a long literal run was
-    // skipped): restart the stream there
-    const uint32_t need_x = L.cx0 + L.ip;
-    const bool jump = need_x >= L.fill;
-    L.fill = jump ? need_x & ~31u : L.fill;
-    L.avail = jump ? L.fill : L.avail;
-    // ring fill: 32 bytes if that leaves every byte from ip on intact, and 32
-    // more if those do too
-    const uint32_t lim = need_x + kRing - 16;
-    const bool fl = (L.ph < P_END) & (L.fill < L.cx0 + L.clen) & (L.fill + 32 <= lim);
-    const bool f2 = fl & (L.fill + 32 < L.cx0 + L.clen) & (L.fill + 64 <= lim);
-    const uint32_t fx = fl ? L.fill : kOff;
-    S.x = fx;
-    S.h2 = f2;
-    S.a = bload16(L.cin, fx);
-    S.b = bload16(L.cin, fl ? fx + 16 : kOff);
-    S.c = bload16(L.cin, f2 ? fx + 32 : kOff);
-    S.d = bload16(L.cin, f2 ? fx + 48 : kOff);
-    L.fill = fl ? L.fill + (f2 ? 64 : 32) : L.fill;
+    fill_issue(L, S, L.cx0 + L.ip, L.ph < P_END);
 }
 
-// DIAG (tuning builds): 1 = no line stores, 2 = every line to the wave's first line,
+// The wave's frames [clo, chi) and item slots [ilo, ihi) as two buffer
+// resources, and lane state at the frame's first byte (L.ring set by the
+// caller); false: the lane has nothing it can parse (ST_NOT_RUN)
+__device__ __forceinline__ bool lane_setup(Lane &L, const FrameDesc &d, bool act, uint64_t rb0, uint32_t cap,
+                                           const uint8_t *comp, uint64_t *items, uint64_t capacity,
+                                           uint64_t clo, uint64_t chi, uint64_t ilo, uint64_t ihi)
+{
+    const uintptr_t cbase = reinterpret_cast<uintptr_t>(comp + clo) & ~(uintptr_t)31;
+    const uint64_t cspan = reinterpret_cast<uintptr_t>(comp + chi) - cbase;
+    // (a span too long for kOff to lie outside it gets no records: its
+    // lanes do not run, and their disabled operations stay disabled)
+    const uint64_t ispan = (ihi - ilo) * 8;
+    const bool fits = cspan < 0x7FFFFF00ull && ispan < 0x7FFFFF00ull;
+    L.cin = __builtin_amdgcn_make_buffer_rsrc((void *)cbase, 0, fits ? (int)(uint32_t)((cspan + 3) & ~3ull) : 0,
+                                              kRsrcDw3);
+    L.irs = __builtin_amdgcn_make_buffer_rsrc((void *)(items + ilo), 0, fits ? (int)(uint32_t)ispan : 0, kRsrcDw3);
+    L.ib = (uint32_t)(rb0 - ilo);
+    L.cx0 = (uint32_t)(reinterpret_cast<uintptr_t>(comp + d.c_off) - cbase);
+    L.clen = d.c_size;
+    L.dlen = d.d_size;
+    L.fill = L.cx0 & ~31u;
+    L.avail = L.fill;
+    L.ph = P_BHDR;
+    L.st = ST_NOT_RUN;
+    L.ip = L.op = L.fail_op = 0;
+    L.csz_flag = 0;
+    L.csize = 0;
+    L.indep = L.bsid = L.max_block = 0;
+    L.iend = L.oend = L.floor_ = L.bop = L.mlim = 0;
+    L.tok = L.lsrc = L.nlit = L.acc = L.moff = 0;
+    L.k = L.kf = 0;
+    L.stop = 0xFFFFFFFFu;
+    L.cap = cap;
+    L.ia = L.ibw = L.ia2 = L.ib2 = L.nk = 0;
+    for (int i = 0; i < kLeanStats; i++)
+        L.cnt[i] = 0;
+    L.why = 0;
+    return act && fits && d.c_size <= kItemPos && rb0 + cap <= capacity;
+}
+
+// the 128 bytes from L.fill into the ring, synchronously
+__device__ __forceinline__ void head_fill(Lane &L)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t fx = L.fill;
+        const u32x4 a = bload16(L.cin, fx), b = bload16(L.cin, fx + 16);
+        ring_put(L, fx, a, b, true);
+        L.fill += 32;
+    }
+    L.avail = L.fill;
+}
+
+// DIAG (tuning builds, launch_lz4_lean's diag with bit 128): 1 = no line stores, 2 = every line to the wave's first line,
 // 4 = sub-step outcome counters (printed), 8 / 16 = a 4- / 1-deep fill pipeline,
 // 32 = one sequence per sub-step (round 3), 64 = every sub-step fills (D = 4:
 // 1.260 ms against 1.085, not kept); a third sequence per sub-step measured
@@ -706,35 +776,8 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (clo == ~0ull)
         return;   // no frame in this wave (inactive lanes stay: flushes take all 64)
     Lane L;
-    const uintptr_t cbase = reinterpret_cast<uintptr_t>(comp + clo) & ~(uintptr_t)31;
-    const uint64_t cspan = reinterpret_cast<uintptr_t>(comp + chi) - cbase;
-    L.cin = __builtin_amdgcn_make_buffer_rsrc((void *)cbase, 0, (int)(uint32_t)((cspan + 3) & ~3ull), kRsrcDw3);
-    const uint64_t ispan = (ihi - ilo) * 8;
-    L.irs = __builtin_amdgcn_make_buffer_rsrc((void *)(items + ilo), 0, (int)(uint32_t)ispan, kRsrcDw3);
-    L.ib = (uint32_t)(rb0 - ilo);
-    L.cx0 = (uint32_t)(reinterpret_cast<uintptr_t>(comp + d.c_off) - cbase);
-    L.clen = d.c_size;
-    L.dlen = d.d_size;
     L.ring = (uint32_t)(uintptr_t)(rings) + threadIdx.x * kStride;
-    L.fill = L.cx0 & ~31u;
-    L.avail = L.fill;
-    L.ph = P_BHDR;
-    L.st = ST_NOT_RUN;
-    L.ip = L.op = L.fail_op = 0;
-    L.csz_flag = 0;
-    L.csize = 0;
-    L.indep = L.bsid = L.max_block = 0;
-    L.iend = L.oend = L.floor_ = L.bop = L.mlim = 0;
-    L.tok = L.lsrc = L.nlit = L.acc = L.moff = 0;
-    L.k = L.kf = 0;
-    L.stop = 0xFFFFFFFFu;
-    L.cap = cap;
-    L.ia = L.ibw = L.ia2 = L.ib2 = L.nk = 0;
-    for (int i = 0; i < kLeanStats; i++)
-        L.cnt[i] = 0;
-    L.why = 0;
-    if (!act || cspan >= 0x7FFFFF00ull || ispan >= 0x7FFFFF00ull || d.c_size > kItemPos ||
-        rb0 + cap > capacity) {
+    if (!lane_setup(L, d, act, rb0, cap, comp, items, capacity, clo, chi, ilo, ihi)) {
         finish(L, ST_NOT_RUN);
     } else if (BLK) {
         // the job's block: its header's 128 bytes synchronously, the frame
@@ -746,24 +789,10 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
         L.indep = (J.info >> 8) & 1;
         L.max_block = 1u << (8 + 2 * L.bsid);
         L.fill = (L.cx0 + J.hpos) & ~31u;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t fx = L.fill;
-            const u32x4 a = bload16(L.cin, fx), b = bload16(L.cin, fx + 16);
-            ring_put(L, fx, a, b, true);
-            L.fill += 32;
-        }
-        L.avail = L.fill;
+        head_fill(L);
     } else {
         // frame header: the first 128 bytes, synchronously
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t fx = L.fill;
-            const u32x4 a = bload16(L.cin, fx), b = bload16(L.cin, fx + 16);
-            ring_put(L, fx, a, b, true);
-            L.fill += 32;
-        }
-        L.avail = L.fill;
+        head_fill(L);
         const int32_t hs = hdr_status(L);
         if (hs >= 0)
             finish(L, hs);
@@ -838,6 +867,252 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
         fail_at[f] = L.fail_op;
 }
 
+// ---- the frame route's parse as two waves per 64 frames ------------------------
+// lz4_lean_pair_kernel: thread t < 256 of the workgroup is the parser of frame
+// blockIdx.x * 256 + t and runs only the chain (fast / put_items / slow);
+// thread t + 256 is that frame's mover and runs only the ring fill and the
+// item flush.  They share the lane's ring and item buffer and talk through a
+// 16-byte mailbox per lane, two 8-byte halves with one writer each:
+//
+//   mover's half   avail  ring coordinates below it are in the ring
+//                  kf     items [0, kf) are out of the item buffer (a multiple of 16)
+//   parser's half  need_x cx0 + ip; never decreases
+//                  k      items written to the item buffer; bit 31 (done): the
+//                         phase is P_DONE and k is final
+//
+// A half is published with a workgroup-scope release store and read with a
+// workgroup-scope acquire load.  A reader may hold a stale half: every word
+// only grows, so a stale one is smaller than the truth, which is the safe
+// side of each rule below.  Nothing depends on which SIMD a wave runs on.
+//
+//   (1) The mover writes ring bytes only below need_x_seen + kRing - 16
+//       (fill_issue's limit).  need_x_seen <= the parser's ip and the parser
+//       reads only coordinates >= ip, so no unread byte is overwritten.
+//   (2) After a jump avail restarts at the new fill position, which is
+//       <= need_x_seen; the old avail was <= need_x_seen too.  A parser
+//       holding either value finds nothing at or past its ip available and
+//       does not use what it reads.
+//   (3) The parser writes item slots k, k + 1 only while k + 2 <= kf_seen + 32
+//       (fast()'s s_cap, slow()'s first test), and kf is published only after
+//       the lines it counts were read out of the buffer.
+//   (4) The mover hands a line over only when k_seen - kf >= 16: all 16
+//       slots of it were written before that k was published.
+constexpr uint32_t kDone = 0x80000000u;
+constexpr uint32_t kPairLds = kLW * 64 * kStride + kLW * 8 * (kFlush + 1) + kLW * 64 * 16;
+static_assert(kPairLds <= 160 * 1024, "the pair parse's LDS exceeds a CU's 160 KB");
+
+__device__ __forceinline__ void mail_put(uint32_t a, uint32_t lo, uint32_t hi)
+{
+    __hip_atomic_store(lp<uint64_t>(a), ((uint64_t)hi << 32) | lo, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ uint64_t mail_get(uint32_t a)
+{
+    return __hip_atomic_load(lp<uint64_t>(a), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// One parser sub-step: up to two sequences against the mailbox's avail and
+// kf, the exact step where some lane needs it, then the new need_x and k.
+template <bool SLOW, bool STATS>
+__device__ __forceinline__ void parser_sub(Lane &L, uint32_t mp, uint32_t mm)
+{
+    const uint64_t m = mail_get(mm);
+    L.avail = (uint32_t)m;
+    L.kf = (uint32_t)(m >> 32);
+    u32x4 dv;
+    const bool live = L.ph != P_DONE;
+    const bool need = fast<false>(L, 0, 0, dv);
+    const bool e1 = L.nk != 0;
+    if (STATS) {
+        L.cnt[0] += live;
+        L.cnt[1] += e1;
+        L.cnt[3] += live && !e1 && !need && (L.why & 1);
+        L.cnt[4] += live && !e1 && !need && (L.why & 128);
+        L.cnt[5] += need;
+    }
+    if (SLOW && __builtin_expect(__ballot(need) != 0, 0)) {
+        if (STATS)
+            L.cnt[8] += 1;
+        if (need)
+            slow(L);
+    }
+    put_items(L);   // rule (3)
+    (void)fast<false>(L, 0, 0, dv);
+    if (STATS) {
+        L.cnt[2] += L.nk != 0;
+        L.cnt[6] += e1 && L.nk == 0 && (L.why & 1);
+        L.cnt[7] += e1 && L.nk == 0 && (L.why & 128);
+    }
+    put_items(L);
+    mail_put(mp, L.cx0 + L.ip, L.k | (L.ph == P_DONE ? kDone : 0u));
+}
+
+// One mover sub-step with pipeline slot S: retire S into the ring (FILL),
+// read the lines handed over last sub-step, publish avail and kf, store the
+// lines, hand over new ones, issue S's next loads (FILL).  L.k and done are
+// the parser's as last seen.
+template <bool FILL>
+__device__ __forceinline__ void mover_sub(Lane &L, Fill &S, bool &done, uint32_t lane, uint32_t tab,
+                                          uint32_t mp, uint32_t mm, uint32_t &fcnt)
+{
+    const uint64_t m = mail_get(mp);
+    const uint32_t need_x = (uint32_t)m;
+    L.k = (uint32_t)(m >> 32) & ~kDone;
+    done = (m >> 63) != 0;
+    if (FILL)
+        fill_retire(L, S);
+    const uint32_t g = lane >> 3, pc = lane & 7;
+    const uint64_t fe = *lp<uint64_t>(tab + 8 * (g < fcnt ? g : kFlush));
+    const u32x4 fv = *lp<u32x4>((uint32_t)fe + 16 * pc);
+    // (after a jump in the last sub-step L.avail is the restart position: rule (2))
+    mail_put(mm, L.avail, L.kf);   // rule (3): L.kf counts lines read by now
+    flush_store<0>(L, fe, fv, g, pc, fcnt);
+    wave_lds_sync();
+    fcnt = flush_hand(L, tab);   // rule (4)
+    wave_lds_sync();
+    if (FILL)
+        fill_issue(L, S, need_x, !done);   // rule (1)
+}
+
+// EVERY: every mover sub-step retires and refills a slot (else every other
+// one, the single-wave kernel's cadence); D: fill pipeline depth.
+template <bool EVERY, int D, bool STATS>
+__global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2))) void lz4_lean_pair_kernel(
+    const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ comp,
+    const uint64_t *__restrict__ rec_base, uint64_t capacity, uint64_t *__restrict__ items,
+    uint32_t *__restrict__ nitems, int32_t *__restrict__ status, uint32_t *__restrict__ fail_at,
+    uint32_t max_csize, uint32_t min_csize)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t rings[kLW * 64 * kStride];
+    __shared__ __attribute__((aligned(16))) uint64_t tabs[kLW * (kFlush + 1)];
+    __shared__ __attribute__((aligned(16))) uint64_t mail_p[kLW * 64], mail_m[kLW * 64];
+    static_assert(sizeof(rings) + sizeof(tabs) + sizeof(mail_p) + sizeof(mail_m) == kPairLds, "LDS layout");
+    constexpr int kPD = 2;   // parser rounds of 2 * kPD sub-steps, as the single-wave kernel's at D = 2
+    const uint32_t t = threadIdx.x & (64 * kLW - 1), lane = threadIdx.x & 63;
+    const bool mover = uni(threadIdx.x) >= 64 * kLW;   // waves 4-7
+    const uint32_t tab = (uint32_t)(uintptr_t)(tabs) + (t >> 6) * 8 * (kFlush + 1);
+    const uint32_t mp = (uint32_t)(uintptr_t)(mail_p) + 8 * t, mm = (uint32_t)(uintptr_t)(mail_m) + 8 * t;
+    const uint32_t f = blockIdx.x * (64 * kLW) + t;
+    FrameDesc d = {0, 0, 0, 0};
+    if (f < n)
+        d = desc[f];
+    // frames of max_csize bytes and more belong to lz4_chunk_kernel, frames
+    // under min_csize to lz4_scan_kernel
+    const bool act = f < n && d.c_size < max_csize && d.c_size >= min_csize;
+    uint64_t rb0 = 0;
+    uint32_t cap = 0;
+    if (act) {
+        rb0 = rec_base[f];
+        cap = slots_of(d.c_size);
+    }
+    // (partner waves hold the same 64 frames: the same spans and step count)
+    const uint64_t clo = uni64(wave_min64(act ? d.c_off : ~0ull));
+    const uint64_t chi = uni64(wave_max64(act ? d.c_off + d.c_size : 0ull));
+    const uint64_t ilo = uni64(wave_min64(act ? rb0 : ~0ull));
+    const uint64_t ihi = uni64(wave_max64(act ? rb0 + cap : 0ull));
+    const uint32_t steps = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(uint32_t)(wave_max64(act ? (uint64_t)d.c_size : 0ull) * 2 + 64 * kPD + 1024));
+    // a wave with no frame issues no memory operation of the parse but
+    // stays for both barriers
+    const bool some = clo != ~0ull;
+    Lane L;
+    L.ring = (uint32_t)(uintptr_t)(rings) + t * kStride;
+    bool ok = false;
+    if (some) {
+        ok = lane_setup(L, d, act, rb0, cap, comp, items, capacity, clo, chi, ilo, ihi);
+        if (!ok)
+            finish(L, ST_NOT_RUN);
+        if (mover) {
+            // frame header: the first 128 bytes, synchronously
+            if (ok)
+                head_fill(L);
+            mail_put(mm, L.avail, 0);
+        } else {
+            mail_put(mp, L.cx0, ok ? 0u : kDone);
+        }
+    }
+    __syncthreads();
+    if (some && mover) {
+        Fill sl[D];
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+            sl[i].x = kOff;
+            sl[i].h2 = false;
+        }
+        uint32_t rounds = 0, fcnt = 0;
+        bool done = !ok;
+        // the table's sink entry names a valid line from the start
+        *lp<uint64_t>(tab + 8 * kFlush) = L.ring + kIBuf;
+        wave_lds_sync();
+        for (;;) {
+#pragma unroll
+            for (int i = 0; i < D; i++) {
+                mover_sub<true>(L, sl[i], done, lane, tab, mp, mm, fcnt);
+                if (!EVERY)
+                    mover_sub<false>(L, sl[i], done, lane, tab, mp, mm, fcnt);
+            }
+            // until every lane is done and has no complete line left; bounded
+            // like the parser's loop, plus the rounds the pipeline may lag it
+            const bool more = !done || L.k - L.kf >= 16;
+            if (!__any(more) || ++rounds > steps + D)
+                break;
+        }
+        // the lines handed over in the last sub-step
+        const uint32_t g = lane >> 3, pc = lane & 7;
+        const uint64_t fe = *lp<uint64_t>(tab + 8 * (g < fcnt ? g : kFlush));
+        const u32x4 fv = *lp<u32x4>((uint32_t)fe + 16 * pc);
+        flush_store<0>(L, fe, fv, g, pc, fcnt);
+        mail_put(mm, L.avail, L.kf);
+    } else if (some) {
+        L.avail = (uint32_t)mail_get(mm);
+        if (ok) {
+            const int32_t hs = hdr_status(L);
+            if (hs >= 0)
+                finish(L, hs);
+        }
+        uint32_t rounds = 0;
+        for (;;) {
+            // as the single-wave kernel: every other sub-step may run the
+            // exact step
+#pragma unroll
+            for (int i = 0; i < kPD; i++) {
+                parser_sub<false, STATS>(L, mp, mm);
+                parser_sub<true, STATS>(L, mp, mm);
+            }
+            const bool busy = L.ph != P_DONE;
+            if (!__any(busy))
+                break;
+            if (++rounds > steps) {
+                if (busy)
+                    L.st = ST_NOT_RUN;
+                break;
+            }
+        }
+        mail_put(mp, L.cx0 + L.ip, L.k | kDone);
+    }
+    // both loops are bounded, so every wave arrives
+    __syncthreads();
+    if (mover || !act)
+        return;
+    // the items the mover did not flush: pairs of slots from the buffer (a
+    // pair past k holds garbage in a slot below cap)
+    const uint32_t kf = (uint32_t)(mail_get(mm) >> 32);
+    for (uint32_t x = kf; x < L.k; x += 2) {
+        const uint32_t a = L.ring + kIBuf + 8 * (x & 31);
+        const u32x4 v = (u32x4){lp<uint32_t>(a)[0], lp<uint32_t>(a)[1],
+                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[0],
+                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[1]};
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), L.irs, 8 * (L.ib + x), 0, 0);
+    }
+    status[f] = L.st;
+    nitems[f] = L.k;
+    if (fail_at)
+        fail_at[f] = L.fail_op;
+    if (STATS)
+        for (int i = 0; i < 9; i++)
+            atomicAdd(&g_lean_stats[i], (unsigned long long)L.cnt[i]);
+}
+
 }   // namespace
 
 int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
@@ -848,12 +1123,41 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
     if (nframes == 0)
         return 0;
     const uint32_t per = 64 * kLW;
-    const dim3 grid((nframes + per - 1) / per), block(per);
+    const dim3 grid((nframes + per - 1) / per);
+#define ZSK_PAIR(E, P, S)                                                                                       \
+    hipLaunchKernelGGL((lz4_lean_pair_kernel<E, P, S>), grid, dim3(2 * per), 0, stream, d_desc, nframes, d_comp, \
+                       rec_base, capacity, items, nitems, d_status, d_fail_at, max_csize, min_csize)
+#ifdef ZSK_TUNING
 #define ZSK_LEAN(D, P)                                                                                         \
-    hipLaunchKernelGGL((lz4_lean_kernel<D, P, false>), grid, block, 0, stream, d_desc, nframes, d_comp, rec_base, \
+    hipLaunchKernelGGL((lz4_lean_kernel<D, P, false>), grid, dim3(per), 0, stream, d_desc, nframes, d_comp, rec_base, \
                        capacity, items, nitems, d_status, d_fail_at, max_csize, min_csize, nullptr, nullptr,       \
                        nullptr)
-#ifdef ZSK_TUNING
+    // bit 128: the single-wave kernel (as the block route runs it), its
+    // diagnostics in the other bits.  Without it the pair kernel: 64 = every
+    // mover sub-step fills, 8 = a 4-deep fill pipeline, 4 = sub-step counters
+    // (printed)
+    if (!(diag & 128)) {
+        if (diag & 4) {
+            unsigned long long z[kLeanStats] = {0};
+            (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_lean_stats), z, sizeof(z), 0, hipMemcpyHostToDevice, stream);
+            ZSK_PAIR(false, 2, true);
+            (void)hipMemcpyFromSymbolAsync(z, HIP_SYMBOL(g_lean_stats), sizeof(z), 0, hipMemcpyDeviceToHost, stream);
+            (void)hipStreamSynchronize(stream);
+            const double fr = nframes;
+            fprintf(stderr, "pair parse per frame: live sub-steps %.1f first emitted %.1f second emitted %.1f; first "
+                            "waits: bytes %.1f flush %.1f exact-needed %.1f; second misses after a first: bytes %.1f "
+                            "flush %.1f; exact-step runs %.1f\n", z[0] / fr, z[1] / fr, z[2] / fr, z[3] / fr, z[4] / fr,
+                    z[5] / fr, z[6] / fr, z[7] / fr, z[8] / fr);
+        } else if ((diag & 72) == 72)
+            ZSK_PAIR(true, 4, false);
+        else if (diag & 64)
+            ZSK_PAIR(true, 2, false);
+        else if (diag & 8)
+            ZSK_PAIR(false, 4, false);
+        else
+            ZSK_PAIR(false, 2, false);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     if (diag & 4) {
         unsigned long long z[kLeanStats] = {0};
         (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_lean_stats), z, sizeof(z), 0, hipMemcpyHostToDevice, stream);
@@ -882,11 +1186,13 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
     else if (diag & 16)
         ZSK_LEAN(0, 1);
     else
-#else
-    (void)diag;
-#endif
         ZSK_LEAN(0, 2);
 #undef ZSK_LEAN
+#else
+    (void)diag;
+    ZSK_PAIR(false, 2, false);
+#endif
+#undef ZSK_PAIR
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -615,7 +615,7 @@ const char *parse_kernel_name(uint32_t nframes, uint32_t c_size, int route)
         return "lz4_lean_kernel (block route)";
     if (c_size >= r.chunk_min)
         return "lz4_chunk_kernel";
-    return c_size >= r.lean_min ? "lz4_lean_kernel" : "lz4_scan_kernel";
+    return c_size >= r.lean_min ? "lz4_lean_pair_kernel" : "lz4_scan_kernel";
 }
 
 int launch_lz4_split(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,

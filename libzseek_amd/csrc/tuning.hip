@@ -85,8 +85,10 @@ int overlapped(uint32_t K, const FrameDesc *d_desc, uint32_t nframes, const uint
 //              section timers)
 //   0x3xx      execute diagnostic version 0x3xx alone (seq_exec.hip: parts of
 //              the dependency rounds removed)
-//   0x2xx      plan + lean parse with diagnostic bits xx (lz4_lean.hip;
-//              0x204 prints sub-step counters)
+//   0x2xx      plan + lean parse with diagnostic bits xx (lz4_lean.hip): 0x200
+//              the pair kernel, 0x280 the single-wave kernel, 0x240 / 0x208 /
+//              0x248 the pair kernel's fill cadences; 0x204 / 0x284 print
+//              the pair / single-wave sub-step counters
 //   0x50K      plan, then K frame chunks, chunk c + 1's lean parse on a
 //              second stream beside chunk c's execute (0x501 = no overlap)
 //   0x400      execute alone with round 0 direct (copy_direct); 0x401 the
