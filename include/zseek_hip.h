@@ -17,6 +17,11 @@
  *                            frame_size_c/d, seek_table.c:204-226.
  *   zsk_pread_device       — zseek_pread (decompress.c:806-824) with the
  *                            decoded bytes left in device memory.
+ *   zsk_preadv, zsk_preadv_device — a caller's loop of zseek_pread calls over
+ *                            scattered ranges (the reference has no vectored
+ *                            read), as one call: the touched frames decoded
+ *                            in one grid per batch; zsk_gather_segments is
+ *                            its device-side segmented copy.
  *   zsk_verify_frame_checksums — the seek table's per-frame checksum,
  *                            parsed by seek_table.c:95-97 and never checked
  *                            there, checked on the GPU.
@@ -153,6 +158,85 @@ ZSEEK_EXPORT int zsk_reader_type(zseek_reader_t *reader);
 ZSEEK_EXPORT ssize_t zsk_pread_device(zseek_reader_t *reader, void *d_buf,
     size_t count, size_t offset, void *call_data,
     char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * Vectored read: @nranges ranges of the decoded file in one call.  Every
+ * frame the ranges touch is read (one pread callback per run of adjacent
+ * touched frames; an untouched frame is never read), decoded once, whole, in
+ * batches of at most zsk_reader_set_batch_bytes decoded bytes, and each
+ * range's bytes are moved to @buf + dst_off by one segmented copy per batch
+ * (zsk_gather_segments).  zsk_preadv: @buf is host memory; zsk_preadv_device:
+ * device memory on the reader's device.  Synchronous.
+ *
+ * Per range, `result` is what looping zseek_pread over it on a reader opened
+ * WITH a cache (cache_size >= 1) delivers in total: the bytes before the
+ * range's first failed frame (a frame with a non-zero status), short at EOF,
+ * 0 for a zero-length range or one at / past EOF, -1 when its first frame
+ * fails.  The no-cache partial-read rules of zseek_pread do not apply: frames
+ * are decoded whole, whatever the reader's cache_size.
+ *
+ * Returns the number of ranges delivered in full (result == min(count,
+ * size - offset), empty ranges included).  When some range failed, @errbuf
+ * holds the text zseek_pread on a cached reader gives for the first failed
+ * frame of the LOWEST-INDEX failed range ("decompress frame: ...").  Returns
+ * -1 with every result -1 when the whole call fails: NULL reader ("invalid
+ * reader"), NULL @ranges with nranges > 0, a pread callback failure ("read
+ * file failed" / "unexpected EOF"), a HIP failure, no device.  nranges == 0
+ * returns 0.
+ *
+ * Ranges may be unsorted, share frames, overlap in the source or repeat.
+ * Their destination regions [dst_off, dst_off + count) must be DISJOINT
+ * (the caller's contract: overlapping destinations are written in no defined
+ * order).  Bytes of a range's destination past `result` are unspecified;
+ * nothing outside a range's own destination region is written.
+ *
+ * The call neither consults nor fills the reader's frame cache
+ * (zseek_reader_stats' cached_frames is unchanged); it takes the reader's
+ * exclusive lock like any decoding read, updates the GPU counters, honours
+ * zsk_reader_set_verify_checksums, and runs on the reader's FIRST lane only
+ * (zsk_reader_set_devices: the first device; a vectored read is not split
+ * over devices).
+ */
+typedef struct {
+    uint64_t offset;   /* decoded offset of the range                         */
+    uint64_t count;    /* bytes wanted                                        */
+    uint64_t dst_off;  /* the range's bytes go to buf + dst_off               */
+    int64_t  result;   /* out: bytes delivered (short at EOF or before a bad  */
+                       /* frame), 0 at/after EOF, -1 if its first frame fails */
+} zsk_range_t;
+
+ZSEEK_EXPORT ssize_t zsk_preadv(zseek_reader_t *reader, void *buf,
+    zsk_range_t *ranges, size_t nranges, void *call_data,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf,
+    zsk_range_t *ranges, size_t nranges, void *call_data,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * The device-side building block, for callers of zsk_*_decode_frames: copy
+ * d_src[src_off, src_off + len) to d_dst[dst_off, dst_off + len) for each of
+ * the @nseg segments in @d_seg (device memory) whose d_status[frame] is
+ * ZSK_OK; a NULL @d_status copies every segment.  Any byte alignment on both
+ * sides, len 0 .. 4 GiB - 1, one to hundreds of thousands of segments per
+ * call; the work is balanced by bytes, not by segment.  The kernel never
+ * writes a byte outside [dst_off, dst_off + len), and reads nothing outside
+ * the aligned 4-byte words that contain bytes of [src_off, src_off + len)
+ * (so @d_src must be readable up to the next 4-byte boundary on both ends,
+ * which holds for any allocation).  Source and destination bytes must not
+ * overlap, and destinations must be disjoint.  Asynchronous on @stream (the
+ * segments are read on the stream too: keep @d_seg alive until it has
+ * passed).  Returns 0 if queued (nseg == 0: nothing to do, 0), -1 otherwise.
+ */
+typedef struct {
+    uint64_t src_off;  /* into d_src                                          */
+    uint64_t dst_off;  /* into d_dst                                          */
+    uint32_t len;      /* bytes                                               */
+    uint32_t frame;    /* index into d_status                                 */
+} zsk_segment_t;
+
+ZSEEK_EXPORT int zsk_gather_segments(const zsk_segment_t *d_seg,
+    uint32_t nseg, const void *d_src, void *d_dst, const int32_t *d_status,
+    void *stream);
 
 /* GPU-side counters of a reader.  zsk_reader_gpu_stats fills the fields
  * through `device` (the struct's layout before copy_threads / io_parts were

@@ -56,6 +56,7 @@
 #include "host.h"
 #include "lane_plan.h"
 #include "pool.h"
+#include "range_plan.h"
 
 using namespace zsk;
 
@@ -259,14 +260,14 @@ bool zstd_partial_ok(int32_t st, uint64_t fail_at, uint64_t end_in_frame)
 // when the block was decoded straight into the destination (room >= max
 // block size) and ERROR_decompressionFailed when it went through its
 // temporary buffer; the room depends on which buffer the block landed in.
-void frame_error(zseek_reader *r, int32_t st, uint32_t fail_at, size_t frame, size_t offset_in_frame,
+void frame_error(zseek_reader *r, bool cached, int32_t st, uint32_t fail_at, size_t frame, size_t offset_in_frame,
                  size_t count, char *errbuf)
 {
     const uint64_t dsize = r->st.dsize(frame);
     const uint64_t at = fail_at;
     const char *prefix;
     uint64_t room;
-    if (r->cache) {
+    if (cached) {
         prefix = "decompress frame";
         room = dsize - at;
     } else if (offset_in_frame > 0 &&
@@ -286,7 +287,7 @@ void frame_error(zseek_reader *r, int32_t st, uint32_t fail_at, size_t frame, si
         // decompress.c:434-451); the discard pass meets a failure whose block
         // starts at or before the prefix's end (a block is decoded as soon
         // as the previous one is flushed)
-        if (!r->cache)
+        if (!cached)
             prefix = offset_in_frame > 0 && at <= offset_in_frame ? "decompress discard data"
                                                                    : "decompress user data";
         set_error(errbuf, "%s: %s", prefix, status_name(st));
@@ -877,7 +878,7 @@ ssize_t pread_frames(zseek_reader *r, void *buf, size_t count, size_t offset, vo
                 return -1;
             }
             if (J.first_bad != SIZE_MAX || J.cached.empty()) {
-                frame_error(r, J.status, J.fail_at, f_first, offset - st.d_off[f_first], count, errbuf);
+                frame_error(r, r->cache != nullptr, J.status, J.fail_at, f_first, offset - st.d_off[f_first], count, errbuf);
                 free_items(J.cached);
                 return -1;
             }
@@ -970,12 +971,320 @@ ssize_t pread_frames(zseek_reader *r, void *buf, size_t count, size_t offset, vo
         if (J.io_failed)
             set_error(errbuf, "%s", J.err);
         else
-            frame_error(r, J.status, J.fail_at, J.first_bad,
+            frame_error(r, r->cache != nullptr, J.status, J.fail_at, J.first_bad,
                         offset > st.d_off[J.first_bad] ? offset - st.d_off[J.first_bad] : 0, count,
                         errbuf);
         return -1;
     }
     return done;
+}
+
+// ---------------------------------------------------------------------------
+// vectored read (zsk_preadv, zsk_preadv_device): range_plan.h's batches
+// through the first lane's slots.  A batch holds only the frames its ranges
+// touch, read run by run and packed back to back; the decode is submit()'s,
+// every frame whole (stop_last off); the bytes leave through the gather
+// kernel (range_gather.hip), segment by segment.
+// ---------------------------------------------------------------------------
+struct VecJob {
+    LaneJob J;   // r, g, call_data, err, io_failed: read_span's context
+    const RangePlan *P = nullptr;
+    uint8_t *buf = nullptr;
+    bool device_dst = false;
+    std::vector<int32_t> status;     // per touched frame (P->frames)
+    std::vector<uint32_t> fail_at;
+};
+
+// Read, upload, decode and gather batch bi on slot s.
+bool submit_gather(VecJob &V, Slot &s, size_t bi)
+{
+    zseek_reader *r = V.J.r;
+    DeviceCtx &g = *V.J.g;
+    const SeekTable &st = r->st;
+    const RangePlan &P = *V.P;
+    const PlanBatch &b = P.batches[bi];
+    const size_t n = b.t1 - b.t0, nseg = b.s1 - b.s0;
+    uint64_t csz = 0;
+    for (size_t t = b.t0; t < b.t1; t++)
+        csz += st.csize(P.frames[t]);
+    const uint64_t dsz = b.d_bytes;
+    const bool ck = r->verify && st.checksum_flag;
+    // a host destination: the segments compacted (in segment order, P.cum)
+    // into the slot's pinned bounce -- by the gather itself through the
+    // bounce's device mapping when the batch is small (download_small's
+    // bound), else compacted behind the decoded bytes in d_out and brought
+    // down by one DMA
+    const uint64_t h_len = V.device_dst ? 0 : b.out_bytes;
+    const uint64_t pack_at = (dsz + 255) & ~255ull;
+    (void)hipSetDevice(g.device);
+    if (h_len > s.h_out_cap)
+        pool_wait(&s.copies);
+    // behind the packed compressed bytes and their 256-byte read slack: the
+    // descriptors, the zstd host plan, the segments, their prefix sum
+    const uint64_t doff = (csz + 256 + 255) & ~255ull;
+    const bool zplan = r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
+    const uint64_t poff = doff + n * sizeof(FrameDesc), goff = poff + (zplan ? 16 * (n + 1) : 0);
+    const uint64_t coff = goff + nseg * sizeof(GatherSeg), up = coff + (nseg + 1) * sizeof(uint64_t);
+    if (!s.reserve(up, pack_at + h_len, h_len, n, ck, V.J.err)) {
+        V.J.io_failed = true;
+        return false;
+    }
+    uint64_t c_at = 0;
+    for (size_t ri = b.r0; ri < b.r1; ri++) {   // one pread per run of adjacent frames
+        const uint64_t c0 = st.c_off[P.runs[ri].f0], len = st.c_off[P.runs[ri].f1] - c0;
+        if (len && !read_span(V.J, s.h_comp + c_at, len, c0)) {
+            V.J.io_failed = true;
+            return false;
+        }
+        c_at += len;
+    }
+    FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + doff);
+    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + doff);
+    uint32_t max_dsize = 0;
+    uint64_t c = 0, d = 0;
+    for (size_t i = 0; i < n; i++) {
+        const size_t f = P.frames[b.t0 + i];
+        FrameDesc &fd = h_desc[i];
+        fd.c_off = c;
+        fd.d_off = d;
+        fd.c_size = (uint32_t)st.csize(f);
+        fd.d_size = (uint32_t)st.dsize(f);
+        c += fd.c_size;
+        d += fd.d_size;
+        max_dsize = std::max(max_dsize, fd.d_size);
+    }
+    GatherSeg *const h_seg = reinterpret_cast<GatherSeg *>(s.h_comp + goff);
+    const uint64_t *const cum = P.cum.data() + b.s0 + bi;
+    for (size_t i = 0; i < nseg; i++) {
+        const PlanSeg &ps = P.segs[b.s0 + i];
+        h_seg[i] = {ps.src_off, V.device_dst ? ps.dst_off : cum[i], ps.len, ps.frame};
+    }
+    memcpy(s.h_comp + coff, cum, (nseg + 1) * sizeof(uint64_t));
+    s.f0 = s.f1 = 0;
+    s.h_from = 0;
+    s.h_len = h_len;
+    s.flagged = false;
+    uint32_t *d_fail = reinterpret_cast<uint32_t *>(s.d_status + n);
+    ZstdHostPlan zp{};
+    if (zplan)
+        zstd_host_plan(h_desc, s.h_comp, (uint32_t)n, reinterpret_cast<uint64_t *>(s.h_comp + poff), &zp);
+    static const bool host_dma = getenv("ZSEEK_HOST_DMA") != nullptr;
+    const uint32_t stop_last = 0xFFFFFFFFu;
+    const bool wave = r->type == ZSEEK_LZ4 && lz4_pick_engine((uint32_t)n) == ENGINE_WAVE;
+    hipError_t e = hipSuccess;
+    if (host_dma)
+        e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, s.stream);
+    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, s.stream) != 0)
+        e = hipErrorLaunchFailure;
+    if (e == hipSuccess && wave)
+        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, n, s.stream);
+    if (e == hipSuccess && wave)
+        e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, n, s.stream);
+    if (e == hipSuccess && r->type == ZSEEK_ZSTD &&
+        (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
+                                            (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
+                                            stop_last)
+               : zstd_decode_frames(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
+                                    stop_last)) != 0)
+        e = hipErrorLaunchFailure;
+    if (e == hipSuccess && r->type == ZSEEK_LZ4) {
+        if (wave) {
+            if (launch_lz4_wave(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
+                e = hipErrorLaunchFailure;
+        } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
+                                         s.stream) != 0) {
+            e = hipErrorOutOfMemory;
+        } else if (launch_lz4_split(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
+                                    ROUTE_AUTO, 15, 0, stop_last, max_dsize, nullptr, nullptr, true) != 0) {
+            e = hipErrorLaunchFailure;
+        }
+    }
+    if (e == hipSuccess && ck) {
+        for (size_t i = 0; i < n; i++)
+            s.h_ck[i] = st.checksum[P.frames[b.t0 + i]];
+        e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
+        if (e == hipSuccess &&
+            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, s.d_ck, s.d_status, s.stream) != 0)
+            e = hipErrorLaunchFailure;
+    }
+    // the segments of the frames that decoded: into the caller's device
+    // buffer, or compacted for the host (the slot's previous batch must have
+    // left the bounce first)
+    if (e == hipSuccess && h_len)
+        pool_wait(&s.copies);
+    if (e == hipSuccess && b.out_bytes) {
+        const bool mapped = h_len && !host_dma && h_len <= kDownloadSmallMax && s.h_out_dev;
+        uint8_t *const dst = V.device_dst ? V.buf : mapped ? static_cast<uint8_t *>(s.h_out_dev) : s.d_out + pack_at;
+        if (launch_range_gather(reinterpret_cast<const GatherSeg *>(s.d_comp + goff),
+                                reinterpret_cast<const uint64_t *>(s.d_comp + coff), (uint32_t)nseg, b.out_bytes,
+                                s.d_out, dst, s.d_status, s.stream) != 0)
+            e = hipErrorLaunchFailure;
+        if (e == hipSuccess && h_len && !mapped)
+            e = hipMemcpyAsync(s.h_out, s.d_out + pack_at, h_len, hipMemcpyDeviceToHost, s.stream);
+    }
+    if (e == hipSuccess &&
+        download_small(reinterpret_cast<uint32_t *>(s.h_status), host_dma ? nullptr : s.h_status_dev,
+                       reinterpret_cast<const uint32_t *>(s.d_status), (uint32_t)(2 * n), nullptr, nullptr, s.d_out, 0,
+                       s.stream) != 0)
+        e = hipErrorLaunchFailure;
+    if (e == hipSuccess)
+        e = hipEventRecord(s.done, s.stream);
+    if (e != hipSuccess) {
+        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
+        V.J.io_failed = true;
+        (void)hipStreamSynchronize(s.stream);
+        return false;
+    }
+    g.batches++;
+    g.frames_decoded += n;
+    g.bytes_decoded += dsz;
+    g.bytes_uploaded += csz;
+    return true;
+}
+
+// Wait for batch bi on slot s: keep its frames' statuses and, for a host
+// destination, scatter the bounce into the caller's buffer on the pool (the
+// segments of failed frames are left out: the gather skipped them).
+bool finish_gather(VecJob &V, Slot &s, size_t bi)
+{
+    const RangePlan &P = *V.P;
+    const PlanBatch &b = P.batches[bi];
+    const size_t n = b.t1 - b.t0;
+    const hipError_t e = hipEventSynchronize(s.done);
+    if (e != hipSuccess) {
+        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
+        V.J.io_failed = true;
+        return false;
+    }
+    for (size_t i = 0; i < n; i++) {
+        V.status[b.t0 + i] = s.h_status[i];
+        V.fail_at[b.t0 + i] = reinterpret_cast<const uint32_t *>(s.h_status + n)[i];
+    }
+    if (V.device_dst || !b.out_bytes)
+        return true;
+    // pieces of >= 256 KiB, about one per pool thread
+    const uint64_t piece = std::max<uint64_t>(256u << 10, b.out_bytes / (uint64_t)copy_pool_threads() + 1);
+    const uint64_t *const cum = P.cum.data() + b.s0 + bi;
+    const PlanSeg *const segs = P.segs.data() + b.s0;
+    const int32_t *const status = V.status.data() + b.t0;
+    const uint8_t *const bounce = s.h_out;
+    uint8_t *const buf = V.buf;
+    const size_t nseg = b.s1 - b.s0;
+    for (size_t i = 0; i < nseg;) {
+        size_t j = i + 1;
+        while (j < nseg && cum[j] - cum[i] < piece)
+            j++;
+        pool_run([=] {
+            for (size_t k = i; k < j; k++)
+                if (status[segs[k].frame] == ST_OK)
+                    memcpy(buf + segs[k].dst_off, bounce + cum[k], segs[k].len);
+        }, &s.copies);
+        i = j;
+    }
+    return true;
+}
+
+ssize_t preadv_frames(zseek_reader *r, void *buf, zsk_range_t *ranges, size_t nranges, void *call_data, char *errbuf,
+                      bool device_dst)
+{
+    static_assert(sizeof(zsk_segment_t) == sizeof(GatherSeg), "segment ABI");
+    for (size_t i = 0; ranges && i < nranges; i++)
+        ranges[i].result = -1;
+    if (!r) {
+        set_error(errbuf, "invalid reader");
+        return -1;
+    }
+    if (nranges == 0)
+        return 0;
+    if (!ranges) {
+        set_error(errbuf, "invalid ranges");
+        return -1;
+    }
+    const SeekTable &st = r->st;
+    std::vector<RangeReq> req(nranges);
+    for (size_t i = 0; i < nranges; i++)
+        req[i] = {ranges[i].offset, ranges[i].count, ranges[i].dst_off};
+    DeviceGuard keep_device;
+    std::unique_lock<std::shared_mutex> guard(r->lock);
+    struct Publish {
+        zseek_reader *r;
+        ~Publish() { publish_stats(r); }
+    } publish{r};
+    const size_t nframes = st.frames();
+    const uint64_t zero = 0;
+    const uint64_t *const d_off = nframes ? st.d_off.data() : &zero;
+    const RangePlan P = plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
+    VecJob V;
+    V.P = &P;
+    V.buf = static_cast<uint8_t *>(buf);
+    V.device_dst = device_dst;
+    V.status.assign(P.frames.size(), ST_NOT_RUN);
+    V.fail_at.assign(P.frames.size(), 0);
+    if (!P.batches.empty()) {
+        if (!buf && !P.segs.empty()) {
+            set_error(errbuf, "invalid buffer");
+            return -1;
+        }
+        for (const PlanBatch &b : P.batches)
+            if (b.s1 - b.s0 >= 0xFFFFFFFFull || b.t1 - b.t0 >= 0x7FFFFFFFull) {
+                set_error(errbuf, "too many ranges");
+                return -1;
+            }
+        if (!ensure_lanes(r, errbuf))
+            return -1;
+        DeviceCtx &g = *r->lanes[0];
+        V.J.r = r;
+        V.J.g = &g;
+        V.J.call_data = call_data;
+        (void)hipSetDevice(g.device);
+        // up to kSlots batches in flight, finished in order (as run_lane)
+        std::deque<std::pair<int, size_t>> inflight;
+        size_t bi = 0;
+        int next = 0;
+        bool stop = false;
+        for (;;) {
+            if (!stop && bi < P.batches.size() && (int)inflight.size() < kSlots) {
+                if (!submit_gather(V, g.slot[next], bi)) {
+                    stop = true;
+                    continue;
+                }
+                inflight.push_back({next, bi});
+                next = (next + 1) % kSlots;
+                bi++;
+                continue;
+            }
+            if (inflight.empty())
+                break;
+            Slot &s = g.slot[inflight.front().first];
+            const size_t done = inflight.front().second;
+            inflight.pop_front();
+            if (stop) {
+                (void)hipEventSynchronize(s.done);
+                continue;
+            }
+            if (!finish_gather(V, s, done))
+                stop = true;
+        }
+        for (Slot &s : g.slot)
+            pool_wait(&s.copies);
+        if (V.J.io_failed) {
+            set_error(errbuf, "%s", V.J.err);
+            return -1;
+        }
+    }
+    std::vector<int64_t> result(nranges);
+    std::vector<size_t> bad(nranges);
+    const size_t ok = range_results(P, req.data(), nranges, d_off, nframes, V.status.data(), result.data(), bad.data());
+    bool reported = false;
+    for (size_t i = 0; i < nranges; i++) {
+        ranges[i].result = result[i];
+        if (bad[i] != SIZE_MAX && !reported) {
+            // the lowest-index failed range: a cached reader's text for the frame
+            frame_error(r, true, V.status[bad[i]], V.fail_at[bad[i]], P.frames[bad[i]], 0, 0, errbuf);
+            reported = true;
+        }
+    }
+    return (ssize_t)ok;
 }
 
 }   // namespace
@@ -1141,6 +1450,27 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_pread_device(zseek_reader_t *reader, void *d
         return 0;
     }
     return pread_frames(reader, d_buf, count, offset, call_data, errbuf, true);
+}
+
+// Vectored reads (zseek_hip.h): many ranges, one decode grid per batch.
+extern "C" ZSEEK_EXPORT ssize_t zsk_preadv(zseek_reader_t *reader, void *buf, zsk_range_t *ranges, size_t nranges,
+                                           void *call_data, char *errbuf)
+{
+    return preadv_frames(reader, buf, ranges, nranges, call_data, errbuf, false);
+}
+
+extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf, zsk_range_t *ranges,
+                                                  size_t nranges, void *call_data, char *errbuf)
+{
+    return preadv_frames(reader, d_buf, ranges, nranges, call_data, errbuf, true);
+}
+
+extern "C" ZSEEK_EXPORT int zsk_gather_segments(const zsk_segment_t *d_seg, uint32_t nseg, const void *d_src,
+                                                void *d_dst, const int32_t *d_status, void *stream)
+{
+    return launch_range_gather(reinterpret_cast<const GatherSeg *>(d_seg), nullptr, nseg, 0,
+                               static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_dst), d_status,
+                               static_cast<hipStream_t>(stream));
 }
 
 // Writes the first `size` bytes of the counters (at most sizeof): a caller

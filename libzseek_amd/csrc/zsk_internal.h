@@ -445,6 +445,21 @@ int launch_lz4_frames_variant(int variant, const FrameDesc *d_desc, uint32_t nfr
 
 const char *status_name(int32_t st);
 
+// Segmented byte copy (range_gather.hip): d_src[src_off, +len) -> d_dst[dst_off,
+// +len) for every segment whose d_status[frame] is ST_OK (d_status NULL: every
+// segment), any alignment, balanced by bytes.  Layout shared with
+// zsk_segment_t (include/zseek_hip.h).  d_cum: the segments' length prefix
+// sum (nseg + 1 entries, device) with `total` = its last entry when the caller
+// has it, else NULL (a scan launch computes it into pooled scratch; total
+// ignored).  Asynchronous on stream; 0 or -1.
+struct GatherSeg {
+    uint64_t src_off, dst_off;
+    uint32_t len, frame;
+};
+static_assert(sizeof(GatherSeg) == 24, "GatherSeg is part of the C ABI");
+int launch_range_gather(const GatherSeg *d_seg, const uint64_t *d_cum, uint32_t nseg, uint64_t total,
+                        const uint8_t *d_src, uint8_t *d_dst, const int32_t *d_status, hipStream_t stream);
+
 // Seek-table checksums (frame_check.hip): frames whose status is ST_OK and
 // whose decoded bytes' XXH64 low 32 bits differ from d_want[f] get
 // ST_SEEK_CHECKSUM.

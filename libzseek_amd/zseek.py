@@ -91,6 +91,12 @@ COMPRESS_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_si
                                 ("flags", "<u4")])
 assert COMPRESS_DESC_DTYPE.itemsize == 24
 COMPRESS_CONTENT_SIZE = 1
+# zsk_range_t: one range of a vectored read (result is written by the call)
+RANGE_DTYPE = np.dtype([("offset", "<u8"), ("count", "<u8"), ("dst_off", "<u8"), ("result", "<i8")])
+assert RANGE_DTYPE.itemsize == 32
+# zsk_segment_t: one copy of zsk_gather_segments
+SEGMENT_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("len", "<u4"), ("frame", "<u4")])
+assert SEGMENT_DTYPE.itemsize == 24
 
 # exported C symbols that include/zseek.h and include/zseek_hip.h declare
 EXPORTED = [
@@ -104,6 +110,7 @@ EXPORTED = [
     "zsk_verify_frame_checksums", "zsk_reader_set_verify_checksums",
     "zsk_reader_set_devices", "zsk_reader_devices", "zsk_reader_set_io_threads",
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
+    "zsk_preadv", "zsk_preadv_device", "zsk_gather_segments",
 ]
 
 _lib = None
@@ -189,6 +196,12 @@ def lib() -> C.CDLL:
     L.zsk_lz4_compress_frames.restype = C.c_int
     L.zsk_lz4_compress_frames.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    for fn in (L.zsk_preadv, L.zsk_preadv_device):
+        fn.restype = C.c_ssize_t
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+    L.zsk_gather_segments.restype = C.c_int
+    L.zsk_gather_segments.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
     _lib = L
     return L
 
@@ -448,6 +461,53 @@ class Reader:
             raise ZseekError(self.error)
         return r
 
+    @staticmethod
+    def _ranges(ranges) -> np.ndarray:
+        """(offset, count[, dst_off]) tuples (dst_off default: back to back in
+        the order given) or a RANGE_DTYPE array -> a fresh RANGE_DTYPE array."""
+        if isinstance(ranges, np.ndarray) and ranges.dtype == RANGE_DTYPE:
+            return np.ascontiguousarray(ranges).copy()
+        out = np.zeros(len(ranges), RANGE_DTYPE)
+        at = 0
+        for i, q in enumerate(ranges):
+            out[i]["offset"], out[i]["count"] = q[0], q[1]
+            out[i]["dst_off"] = q[2] if len(q) > 2 else at
+            at += q[1]
+        return out
+
+    def preadv_raw(self, buf_ptr: int, ranges: np.ndarray, device: bool = False) -> int:
+        """zsk_preadv / zsk_preadv_device on a RANGE_DTYPE array (its `result`
+        fields are written); returns the C return value."""
+        fn = lib().zsk_preadv_device if device else lib().zsk_preadv
+        return fn(self._h, buf_ptr, ranges.ctypes.data if ranges.size else None, ranges.size, None,
+                  self._err)
+
+    def preadv(self, ranges) -> tuple[list, int]:
+        """zsk_preadv: many ranges, one decode grid per batch.  `ranges`:
+        (offset, count) pairs.  -> ([bytes delivered per range, None for a
+        range whose first frame failed], ranges delivered in full);
+        ``self.error`` holds the text for the first failed range.  ZseekError
+        when the whole call fails."""
+        rg = self._ranges([(q[0], q[1]) for q in ranges])
+        out = np.empty(max(int(rg["count"].sum()), 1), np.uint8)
+        n_ok = self.preadv_raw(out.ctypes.data, rg)
+        if n_ok < 0:
+            raise ZseekError(self.error)
+        got = [None if q["result"] < 0 else
+               out[int(q["dst_off"]): int(q["dst_off"]) + int(q["result"])].tobytes() for q in rg]
+        return got, n_ok
+
+    def preadv_device(self, dev_ptr: int, ranges) -> tuple[np.ndarray, int]:
+        """zsk_preadv_device: the ranges' bytes to device memory at dev_ptr +
+        dst_off.  `ranges`: (offset, count, dst_off) tuples or a RANGE_DTYPE
+        array.  -> (the RANGE_DTYPE array with `result` filled, ranges
+        delivered in full)."""
+        rg = self._ranges(ranges)
+        n_ok = self.preadv_raw(dev_ptr, rg, device=True)
+        if n_ok < 0:
+            raise ZseekError(self.error)
+        return rg, n_ok
+
     def stats(self) -> dict:
         s = ReaderStatsC()
         if not lib().zseek_reader_stats(self._h, C.byref(s), self._err):
@@ -613,6 +673,24 @@ def verify_frame_checksums(desc, out, checksums, status, stream: int | None = No
     if lib().zsk_verify_frame_checksums(desc.data_ptr(), n, out.data_ptr(), checksums.data_ptr(),
                                         status.data_ptr(), stream) != 0:
         raise ZseekError("zsk_verify_frame_checksums launch failed")
+
+
+def gather_segments(seg, src, dst, status=None, stream: int | None = None) -> None:
+    """zsk_gather_segments on torch device tensors (async): seg = N x 24-byte
+    zsk_segment_t (uint8, SEGMENT_DTYPE); copies src[src_off, +len) to
+    dst[dst_off, +len) for every segment whose status[frame] is 0 (status
+    None: every segment)."""
+    import torch
+    if seg.numel() % 24:
+        raise ValueError("seg must hold 24 bytes per segment")
+    for t in (seg, src, dst) + (() if status is None else (status,)):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("gather_segments needs contiguous device tensors")
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if lib().zsk_gather_segments(seg.data_ptr(), seg.numel() // 24, src.data_ptr(), dst.data_ptr(),
+                                 None if status is None else status.data_ptr(), stream) != 0:
+        raise ZseekError("zsk_gather_segments launch failed")
 
 
 def lz4_compress_bound(n: int) -> int:
