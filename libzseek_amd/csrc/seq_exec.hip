@@ -1,7 +1,8 @@
 // seq_exec.hip — the execute phase's launchers and the one-frame route's
 // executes (gfx950): seq_exec_frame_kernel (a frame of <= 64 KiB staged whole
-// in LDS per workgroup) and seq_exec_big_kernel (bigger frames through a
-// sliding 64 KiB window).  The throughput kernel seq_exec_kernel<OUTB, SEG> and its
+// in LDS per workgroup), seq_exec_big_kernel (bigger frames through a
+// sliding 64 KiB window) and seq_exec_blocks_kernel (a block of a bigger
+// frame per workgroup), over the pieces they share.  The throughput kernel seq_exec_kernel<OUTB, SEG> and its
 // helpers live in seq_exec_dev.h (shared with seq_exec_seg.hip and the
 // tuning build's seq_exec_tune.hip, which holds the diagnostic variants).
 #include <hip/hip_runtime.h>
@@ -102,6 +103,267 @@ __device__ __forceinline__ void lcopy(uint32_t dst, uint32_t src, uint32_t n, ui
     }
 }
 
+// ---- the pieces the three workgroup executes share ----
+// seq_exec_frame_kernel, seq_exec_big_kernel and seq_exec_blocks_kernel each
+// stage a frame, a window or a block in LDS and give every thread two
+// sequences of a batch of 2,048; what they do alike is defined here once
+// (but the frame kernel's own pass loop: see match_passes).
+
+// exclusive scan of v over the workgroup, in thread order; total: the sum.
+// Every thread calls it (two workgroup barriers); wsum: a word per wave
+__device__ __forceinline__ uint32_t wg_scan(uint32_t v, uint32_t &total, uint32_t *wsum)
+{
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_add(v);
+    if (lane == 63)
+        wsum[wv] = inc;
+    __syncthreads();
+    uint32_t before = 0, tot = 0;
+    for (uint32_t k = 0; k < kFT / 64; k++) {
+        const uint32_t x = wsum[k];
+        before += k < wv ? x : 0;
+        tot += x;
+    }
+    __syncthreads();
+    total = tot;
+    return before + inc - v;
+}
+
+// a bit per staged byte in an LDS word array w (done bits, taint bits): set
+// bits [a, a + len), and whether all / any of them are set -- relaxed reads of
+// every word (no early exit, so they are in flight together)
+__device__ __forceinline__ void bits_or(uint32_t *w, uint32_t a, uint32_t len)
+{
+    for (const uint32_t e = a + len; a < e;) {
+        const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
+        __hip_atomic_fetch_or(&w[a >> 5], nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_WORKGROUP);
+        a += nb;
+    }
+}
+
+__device__ __forceinline__ bool all_set(uint32_t *w, uint32_t a, uint32_t len)
+{
+    bool all = true;
+    for (const uint32_t e = a + len; a < e;) {
+        const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
+        const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
+        all &= (__hip_atomic_load(&w[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) == m;
+        a += nb;
+    }
+    return all;
+}
+
+__device__ __forceinline__ bool any_set(uint32_t *w, uint32_t a, uint32_t len)
+{
+    bool any = false;
+    for (const uint32_t e = a + len; a < e;) {
+        const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
+        const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
+        any |= (__hip_atomic_load(&w[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) != 0;
+        a += nb;
+    }
+    return any;
+}
+
+// staged bytes [a, a + len) are written: one release fence, then relaxed bit
+// sets
+__device__ __forceinline__ void mark_bytes(uint32_t *done, uint32_t a, uint32_t len)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    bits_or(done, a, len);
+}
+
+// ... and whether they all are: one acquire fence once all are set
+__device__ __forceinline__ bool ready_bytes(uint32_t *done, uint32_t a, uint32_t len)
+{
+    const bool all = all_set(done, a, len);
+    if (all)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return all;
+}
+
+// one run's done bits [a, a + len), len > 0, by the whole wave: a word a lane
+// a step (a, len wave-uniform; the caller has fenced)
+__device__ __forceinline__ void mark_run_wave(uint32_t *done, uint32_t a, uint32_t len, uint32_t lane)
+{
+    const uint32_t e = a + len - 1;
+    for (uint32_t g = (a >> 5) + lane; g <= e >> 5; g += 64) {
+        const uint32_t lo = g == a >> 5 ? a & 31 : 0, hi = g == e >> 5 ? e & 31 : 31;
+        const uint32_t m = hi - lo == 31 ? 0xFFFFFFFFu : ((1u << (hi - lo + 1)) - 1) << lo;
+        __hip_atomic_fetch_or(&done[g], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+// each lane's literal run [a, a + L) is written (L == 0: none): the runs
+// longer than kFLong marked by the whole wave, as they were copied, the
+// others by their lanes
+__device__ __forceinline__ void mark_lit_runs(uint32_t *done, uint32_t a, uint32_t L, uint32_t lane)
+{
+    const bool coop = L > kFLong;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
+        const int q = (int)__builtin_ctzll(lm);
+        mark_run_wave(done, lane_val(a, q), lane_val(L, q), lane);
+    }
+    if (!coop && L)
+        mark_bytes(done, a, L);
+}
+
+// a sequence of the item list: literal length, match length, offset and the
+// literals' place in the literal source
+struct Seq {
+    uint32_t lit, ml, off, src;
+};
+
+// item i of nit; all zero past the list and for the second half of an
+// extended item.  slot maps an item index onto its place in `it` (the
+// identity, or seq_exec_big_kernel's job table)
+template <typename Slot>
+__device__ __forceinline__ Seq load_seq(const uint64_t *it, uint32_t i, uint32_t nit, Slot slot)
+{
+    Seq s = {0, 0, 0, 0};
+    if (i < nit) {
+        const uint32_t si = slot(i);
+        const uint64_t cur = it[si];
+        const uint32_t c0 = (uint32_t)cur, c1 = (uint32_t)(cur >> 32);
+        const bool second = i > 0 && ((uint32_t)it[slot(i - 1)] & kItemExt);   // an extended item's second half
+        if (!second) {
+            s.src = c0 & kItemPos;
+            if (c0 & kItemExt) {
+                const uint64_t nx = it[si + 1];
+                s.lit = (uint32_t)nx;
+                s.ml = (uint32_t)(nx >> 32);
+                s.off = c1;
+            } else {
+                s.lit = (c1 >> 16) & 0xFF;
+                const uint32_t mc = c1 >> 24;
+                s.ml = mc ? mc + 3 : 0;
+                s.off = c1 & 0xFFFF;
+            }
+        }
+    }
+    return s;
+}
+
+struct SameSlot {   // items contiguous in `it`
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return i; }
+};
+
+// each lane's literal run from HBM into LDS: L bytes (0: none) at src of the
+// literal source to LDS address dst.  A run longer than kFLong is copied by
+// the whole wave, 1 KiB per step (one lane's serial copy of a ~1 KiB run was
+// the literal phase's critical path); the others by their lanes, up to 64
+// bytes per step, four 16-byte loads in flight
+__device__ __forceinline__ void lit_runs_hbm(const Span &lsp, uint32_t dst, uint32_t src, uint32_t L, uint32_t lane)
+{
+    const bool coop = L > kFLong;
+    for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
+        const int q = (int)__builtin_ctzll(lm);
+        const uint32_t d0 = lane_val(dst, q), s = lane_val(src, q), n = lane_val(L, q);
+        for (uint32_t k = 16 * lane; k < n; k += 1024)
+            lds_put(d0 + k, load16u(lsp.r, lsp.s0 + s + k), min(16u, n - k));
+    }
+    if (!coop && L) {
+        for (uint32_t k = 0; k < L; k += 64) {
+            u32x4 v[4];
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++)
+                v[q] = load16u(lsp.r, k + 16 * q < L ? lsp.s0 + src + k + 16 * q : kBad);
+#pragma unroll
+            for (uint32_t q = 0; q < 4; q++)
+                if (k + 16 * q < L)
+                    lds_put(dst + k + 16 * q, v[q], min(16u, L - k - 16 * q));
+        }
+    }
+}
+
+// the decoded end: e is the end of this thread's sequences (0: none); a wave
+// max, one LDS atomic per wave (2,048 atomics on one word cost ~20K cycles per
+// frame)
+__device__ __forceinline__ void note_end(uint32_t *hi_end, uint32_t e, uint32_t lane)
+{
+    const uint32_t we = wave_incl_max(e);
+    if (lane == 63 && we)
+        atomicMax(hi_end, we);
+}
+
+// a match of m bytes at LDS address db from ov bytes before it, every byte it
+// reads final (the first min(ov, m) of them written by others, the rest by
+// this copy)
+__device__ __forceinline__ void copy_match(uint32_t db, uint32_t ov, uint32_t m)
+{
+    const uint32_t sb = db - ov;
+    if (ov >= m && m <= 128) {
+        scopy(db, sb, min(m, 64u));
+        if (m > 64)
+            scopy(db + 64, sb + 64, m - 64);
+    } else if (ov >= m || ov >= 16) {   // apart, or trailing by >= 16: pieces ahead of their sources
+        lcopy(db, sb, m, ov >= m ? 64u : min(64u, ov & ~15u));
+    } else {
+        // overlapping: the first e = ov * ceil(16 / ov) bytes one at a time,
+        // then 16-byte pieces trailing by e (each reads bytes an earlier step
+        // of this thread wrote)
+        const uint32_t e = ov * ((16 + ov - 1) / ov);
+        const uint32_t h = min(e, m);
+        for (uint32_t k = 0; k < h; k++) {
+            *lp<uint8_t>(db + k) = *lp<uint8_t>(sb + k);
+            wave_lds_sync();
+        }
+        for (uint32_t k = h; k < m; k += 16) {
+            lds_put(db + k, lds16(db + k - e), min(16u, m - k));
+            wave_lds_sync();
+        }
+    }
+}
+
+// n staged bytes at LDS address a out to o + x, by the workgroup (t: the
+// thread): a byte head to 16-byte alignment, whole 16-byte stores, a byte
+// tail.  (o and x apart, as the window kernel has them: handed o + H as one
+// pointer, seq_exec_big_kernel, at its 128 VGPRs, spills one more)
+__device__ __forceinline__ void put_out(uint8_t *o, uint32_t x, uint32_t a, uint32_t n, uint32_t t)
+{
+    const uint32_t head = min(n, (uint32_t)((16 - ((uintptr_t)(o + x) & 15)) & 15));
+    if (t < head)
+        o[x + t] = *lp<uint8_t>(a + t);
+    const uint32_t nchunks = (n - head) / 16;
+    for (uint32_t c = t; c < nchunks; c += kFT)
+        *reinterpret_cast<u32x4 *>(o + x + head + 16 * c) = lds16(a + head + 16 * c);
+    const uint32_t tail0 = head + 16 * nchunks;
+    if (tail0 + t < n)
+        o[x + tail0 + t] = *lp<uint8_t>(a + tail0 + t);
+}
+
+// a wave's match passes (seq_exec_big_kernel, seq_exec_blocks_kernel; the
+// frame kernel has its own copy of this loop): the wave loops on its own
+// until its matches are copied (no workgroup barrier per round: a wave whose
+// sources are ready runs ahead; one that made no progress sleeps a little).
+// step(q, pending) copies and marks the thread's match q if it is pending and
+// its source is ready, and says whether it did; every lane calls it for both
+// q each pass, pending or not (a step may have a part the whole wave takes).
+// The step is told `pending` and does not capture pend: an array a closure
+// holds by reference is no longer kept in registers when q is not unrolled
+// (seq_exec_blocks_kernel: 8 bytes of scratch).  Returns the wave's passes.
+template <typename Step>
+__device__ __forceinline__ uint32_t match_passes(bool (&pend)[2], Step step)
+{
+    for (uint32_t pass = 0;; pass++) {
+        bool moved = false;
+        for (int q = 0; q < 2; q++) {
+            if (step(q, pend[q])) {
+                pend[q] = false;
+                moved = true;
+            }
+        }
+        // (validated items always drain; the bound only guards the GPU
+        // against a malformed list)
+        if (!__any(pend[0] || pend[1]) || pass > (1u << 22))
+            return pass + 1;
+        if (!__any(moved))
+            __builtin_amdgcn_s_sleep(1);
+    }
+}
+
 __global__ __launch_bounds__(kFT) void seq_exec_frame_kernel(
     const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ comp, uint8_t *__restrict__ out,
     const uint64_t *__restrict__ rec_base, const uint64_t *__restrict__ items, const uint32_t *__restrict__ nitems,
@@ -194,73 +456,15 @@ __global__ __launch_bounds__(kFT) void seq_exec_frame_kernel(
     __syncthreads();
     ZSK_FT(0)
 
-    auto scan = [&](uint32_t v, uint32_t &total) -> uint32_t {   // exclusive, in thread order
-        const uint32_t inc = wave_incl_add(v);
-        if (lane == 63)
-            wsum[wv] = inc;
-        __syncthreads();
-        uint32_t before = 0, tot = 0;
-        for (uint32_t k = 0; k < kFT / 64; k++) {
-            const uint32_t x = wsum[k];
-            before += k < wv ? x : 0;
-            tot += x;
-        }
-        __syncthreads();
-        total = tot;
-        return before + inc - v;
-    };
-    // one release fence, then relaxed bit sets; readiness: relaxed reads of
-    // every word (no early exit, so they are in flight together), one acquire
-    // fence once all are set
-    auto mark = [&](uint32_t a, uint32_t len) {   // output bytes [a, a + len) written
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        for (const uint32_t e = a + len; a < e;) {
-            const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-            __hip_atomic_fetch_or(&done[a >> 5], nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_WORKGROUP);
-            a += nb;
-        }
-    };
-    auto ready = [&](uint32_t a, uint32_t len) -> bool {
-        bool all = true;
-        for (const uint32_t e = a + len; a < e;) {
-            const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-            const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
-            all &= (__hip_atomic_load(&done[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) == m;
-            a += nb;
-        }
-        if (all)
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        return all;
-    };
     uint32_t base_op = 0;
     for (uint32_t w0 = 0; w0 < nit && base_op < stop; w0 += 2 * kFT) {
         uint32_t lit[2], ml[2], off[2], src[2], op[2], tot[2];
         for (int j = 0; j < 2; j++) {
-            const uint32_t i = w0 + j * kFT + t;
-            lit[j] = ml[j] = off[j] = src[j] = 0;
-            if (i < nit) {
-                const uint64_t cur = it[i];
-                const uint32_t c0 = (uint32_t)cur, c1 = (uint32_t)(cur >> 32);
-                const bool second = i > 0 && ((uint32_t)it[i - 1] & kItemExt);   // an extended item's second half
-                if (!second) {
-                    src[j] = c0 & kItemPos;
-                    if (c0 & kItemExt) {
-                        const uint64_t nx = it[i + 1];
-                        lit[j] = (uint32_t)nx;
-                        ml[j] = (uint32_t)(nx >> 32);
-                        off[j] = c1;
-                    } else {
-                        lit[j] = (c1 >> 16) & 0xFF;
-                        const uint32_t mc = c1 >> 24;
-                        ml[j] = mc ? mc + 3 : 0;
-                        off[j] = c1 & 0xFFFF;
-                    }
-                }
-            }
+            const Seq s = load_seq(it, w0 + j * kFT + t, nit, SameSlot{});
+            lit[j] = s.lit, ml[j] = s.ml, off[j] = s.off, src[j] = s.src;
         }
-        const uint32_t x0 = scan(lit[0] + ml[0], tot[0]);
-        const uint32_t x1 = scan(lit[1] + ml[1], tot[1]);
+        const uint32_t x0 = wg_scan(lit[0] + ml[0], tot[0], wsum);
+        const uint32_t x1 = wg_scan(lit[1] + ml[1], tot[1], wsum);
         ZSK_FT(1)
         op[0] = base_op + x0;
         op[1] = base_op + tot[0] + x1;
@@ -296,66 +500,30 @@ __global__ __launch_bounds__(kFT) void seq_exec_frame_kernel(
                     for (uint32_t k = 0; k < L; k += 16)
                         lds_put(ob0 + op[j] + k, load16u(lsp.r, lsp.s0 + src[j] + k), min(16u, L - k));
             }
-            if (!ZSK_FD(2)) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
-                    const int q = (int)__builtin_ctzll(lm);
-                    const uint32_t a = lane_val(op[j], q), e = a + lane_val(L, q) - 1;
-                    for (uint32_t g = (a >> 5) + lane; g <= e >> 5; g += 64) {
-                        const uint32_t lo = g == a >> 5 ? a & 31 : 0, hi = g == e >> 5 ? e & 31 : 31;
-                        const uint32_t m = hi - lo == 31 ? 0xFFFFFFFFu : ((1u << (hi - lo + 1)) - 1) << lo;
-                        __hip_atomic_fetch_or(&done[g], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (!coop && L)
-                    mark(op[j], L);
-            }
+            if (!ZSK_FD(2))
+                mark_lit_runs(done, op[j], L, lane);
             pend[j] = on && ml[j] != 0 && !ZSK_FD(4);
         }
         {
-            // the decoded end: a wave max, one LDS atomic per wave (2,048
-            // atomics on one word cost ~20K cycles per frame)
             const bool on0 = op[0] < stop && lit[0] + ml[0] != 0, on1 = op[1] < stop && lit[1] + ml[1] != 0;
-            const uint32_t e = max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u);
-            const uint32_t we = wave_incl_max(e);
-            if (lane == 63 && we)
-                atomicMax(&hi_end, we);
+            note_end(&hi_end, max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u), lane);
         }
         __syncthreads();
         ZSK_FT(2)
-        // each wave loops on its own until its matches are copied (no
-        // workgroup barrier per round: a wave whose sources are ready runs
-        // ahead; one that made no progress sleeps a little)
+        // a match copies once its source's first min(off, ml) bytes are done.
+        // This kernel keeps its own copy of match_passes' loop: through the
+        // shared one it measured 0.2-0.5 us (1 %) slower on 64 KiB LZ4 frames
+        // at equal instruction counts
         for (uint32_t pass = 0;; pass++) {
             bool moved = false;
             for (int j = 0; j < 2; j++) {
                 if (!pend[j])
                     continue;
                 const uint32_t mb = op[j] + lit[j], o = off[j], m = ml[j];
-                if (!ready(mb - o, o >= m ? m : o))
+                if (!ready_bytes(done, mb - o, o >= m ? m : o))
                     continue;
-                if (o >= m && m <= 128) {
-                    scopy(ob0 + mb, ob0 + mb - o, min(m, 64u));
-                    if (m > 64)
-                        scopy(ob0 + mb + 64, ob0 + mb - o + 64, m - 64);
-                } else if (o >= m || o >= 16) {   // apart, or trailing by >= 16: pieces ahead of their sources
-                    lcopy(ob0 + mb, ob0 + mb - o, m, o >= m ? 64u : min(64u, o & ~15u));
-                } else {
-                    // overlapping: the first e = o * ceil(16 / o) bytes one at a
-                    // time, then 16-byte pieces trailing by e (each reads bytes
-                    // an earlier step of this thread wrote)
-                    const uint32_t e = o >= 16 ? o : o * ((16 + o - 1) / o);
-                    const uint32_t h = o >= 16 ? 0 : min(e, m);
-                    for (uint32_t k = 0; k < h; k++) {
-                        ob[mb + k] = ob[mb - o + k];
-                        wave_lds_sync();
-                    }
-                    for (uint32_t k = h; k < m; k += 16) {
-                        lds_put(ob0 + mb + k, lds16(ob0 + mb + k - e), min(16u, m - k));
-                        wave_lds_sync();
-                    }
-                }
-                mark(mb, m);
+                copy_match(ob0 + mb, o, m);
+                mark_bytes(done, mb, m);
                 pend[j] = false;
                 moved = true;
             }
@@ -380,19 +548,8 @@ __global__ __launch_bounds__(kFT) void seq_exec_frame_kernel(
         base_op += tot[0] + tot[1];
     }
     __syncthreads();
-    // the decoded bytes [0, hi_end) out: a byte head to 16-byte alignment,
-    // whole 16-byte stores, a byte tail
-    const uint32_t E = min(hi_end, d.d_size);
-    uint8_t *o = out + d.d_off;
-    const uint32_t head = min(E, (uint32_t)((16 - ((uintptr_t)o & 15)) & 15));
-    if (t < head)
-        o[t] = ob[t];
-    const uint32_t nchunks = (E - head) / 16;
-    for (uint32_t c = t; c < nchunks; c += kFT)
-        *reinterpret_cast<u32x4 *>(o + head + 16 * c) = lds16(ob0 + head + 16 * c);
-    const uint32_t tail0 = head + 16 * nchunks;
-    if (tail0 + t < E)
-        o[tail0 + t] = ob[tail0 + t];
+    // the decoded bytes [0, hi_end) out
+    put_out(out + d.d_off, 0, ob0, min(hi_end, d.d_size), t);
     if (post.h_flag) {
         // a lone frame's results to the host from the staged output (the
         // request's bytes; past E they are whatever LDS holds, as HBM's would
@@ -423,12 +580,13 @@ __global__ __launch_bounds__(kFT) void seq_exec_frame_kernel(
 // seq_exec_frame_kernel, through a sliding window: LDS holds the 64 KiB of
 // output before the window (every byte final: LZ4's offsets reach 65,535
 // back) and the window itself, 64 KiB at frame offset H.  A batch of 2,048
-// items is placed by the same workgroup scan and cut before the first item
-// that would end past the window; literal runs are copied from HBM (the
-// compressed frame does not fit beside the window), matches resolve in the
-// per-wave passes over the window's done bits, a source byte before H
-// always ready.  Then the window's bytes go out and it slides to the first
-// byte not decoded (the 64 KiB before it moved down as the new history).
+// items is placed by the workgroup scan (wg_scan) and cut before the first
+// item that would end past the window; literal runs are copied from HBM
+// (lit_runs_hbm: the compressed frame does not fit beside the window),
+// matches resolve in the per-wave passes (match_passes) over the window's
+// done bits, a source byte before H always ready.  Then the window's bytes
+// go out (put_out) and it slides to the first byte not decoded (the 64 KiB
+// before it moved down as the new history).
 // Items: contiguous (rec_base[f]), or -- a frame the block route accepted
 // (bfirst[f] != kNoJob, the job parse of lz4_chunk.hip) -- job by job, item
 // index i mapped onto its job's slots through a table of the jobs' first
@@ -538,59 +696,6 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
         ZSK_BT(0)
         ZSK_BC(8)
 
-        auto scan = [&](uint32_t v, uint32_t &total) -> uint32_t {   // exclusive, in thread order
-            const uint32_t inc = wave_incl_add(v);
-            if (lane == 63)
-                wsum[wv] = inc;
-            __syncthreads();
-            uint32_t before = 0, tot = 0;
-            for (uint32_t k = 0; k < kFT / 64; k++) {
-                const uint32_t x = wsum[k];
-                before += k < wv ? x : 0;
-                tot += x;
-            }
-            __syncthreads();
-            total = tot;
-            return before + inc - v;
-        };
-        auto mark = [&](uint32_t a, uint32_t len) {   // window bytes [a, a + len) written
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            for (const uint32_t e = a + len; a < e;) {
-                const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-                __hip_atomic_fetch_or(&done[a >> 5], nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0, __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_WORKGROUP);
-                a += nb;
-            }
-        };
-        auto ready = [&](uint32_t a, uint32_t len) -> bool {   // window bytes
-            bool all = true;
-            for (const uint32_t e = a + len; a < e;) {
-                const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-                const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
-                all &= (__hip_atomic_load(&done[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) == m;
-                a += nb;
-            }
-            if (all)
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            return all;
-        };
-        // frame bytes [a, e) of the window out: a byte head to 16-byte
-        // alignment, whole 16-byte stores, a byte tail
-        auto put_out = [&](uint32_t H, uint32_t a, uint32_t e) {
-            if (e <= a)
-                return;
-            const uint32_t head = min(e - a, (uint32_t)((16 - ((uintptr_t)(o + a) & 15)) & 15));
-            const uint32_t w = kBWin + a - H;
-            if (t < head)
-                o[a + t] = ob[w + t];
-            const uint32_t nchunks = (e - a - head) / 16;
-            for (uint32_t c = t; c < nchunks; c += kFT)
-                *reinterpret_cast<u32x4 *>(o + a + head + 16 * c) = lds16(ob0 + w + head + 16 * c);
-            const uint32_t tail0 = head + 16 * nchunks;
-            if (tail0 + t < e - a)
-                o[a + tail0 + t] = ob[w + tail0 + t];
-        };
-
         uint32_t H = 0, P = 0, w0 = 0;   // window start, bytes decoded, next item
         bool stuck = false;
         while (w0 < nit && P < stop) {
@@ -600,32 +705,12 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
             }
             uint32_t lit[2], ml[2], off[2], src[2], op[2], tot[2], idx[2];
             for (int j = 0; j < 2; j++) {
-                const uint32_t i = w0 + j * kFT + t;
-                idx[j] = i;
-                lit[j] = ml[j] = off[j] = src[j] = 0;
-                if (i < nit) {
-                    const uint32_t si = slot(i);
-                    const uint64_t cur = it[si];
-                    const uint32_t c0 = (uint32_t)cur, c1 = (uint32_t)(cur >> 32);
-                    const bool second = i > 0 && ((uint32_t)it[slot(i - 1)] & kItemExt);   // an extended item's second half
-                    if (!second) {
-                        src[j] = c0 & kItemPos;
-                        if (c0 & kItemExt) {
-                            const uint64_t nx = it[si + 1];
-                            lit[j] = (uint32_t)nx;
-                            ml[j] = (uint32_t)(nx >> 32);
-                            off[j] = c1;
-                        } else {
-                            lit[j] = (c1 >> 16) & 0xFF;
-                            const uint32_t mc = c1 >> 24;
-                            ml[j] = mc ? mc + 3 : 0;
-                            off[j] = c1 & 0xFFFF;
-                        }
-                    }
-                }
+                idx[j] = w0 + j * kFT + t;
+                const Seq s = load_seq(it, idx[j], nit, slot);
+                lit[j] = s.lit, ml[j] = s.ml, off[j] = s.off, src[j] = s.src;
             }
-            const uint32_t x0 = scan(lit[0] + ml[0], tot[0]);
-            const uint32_t x1 = scan(lit[1] + ml[1], tot[1]);
+            const uint32_t x0 = wg_scan(lit[0] + ml[0], tot[0], wsum);
+            const uint32_t x1 = wg_scan(lit[1] + ml[1], tot[1], wsum);
             ZSK_BT(1)
             ZSK_BC(7)
             op[0] = P + x0;
@@ -646,88 +731,28 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
             for (int j = 0; j < 2; j++) {
                 const bool on = op[j] < lim && lit[j] + ml[j] != 0;
                 const uint32_t L = on ? lit[j] : 0;
-                const uint32_t dst = C + op[j] - H;
-                const bool coop = L > kFLong;   // (as seq_exec_frame_kernel)
-                for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
-                    const int q = (int)__builtin_ctzll(lm);
-                    const uint32_t d0 = lane_val(dst, q), s = lane_val(src[j], q), nq = lane_val(L, q);
-                    for (uint32_t k = 16 * lane; k < nq; k += 1024)
-                        lds_put(d0 + k, load16u(lsp.r, lsp.s0 + s + k), min(16u, nq - k));
-                }
-                if (!coop && L) {
-                    // up to 64 bytes per step, four 16-byte loads in flight
-                    for (uint32_t k = 0; k < L; k += 64) {
-                        u32x4 v[4];
-    #pragma unroll
-                        for (uint32_t q = 0; q < 4; q++)
-                            v[q] = load16u(lsp.r, k + 16 * q < L ? lsp.s0 + src[j] + k + 16 * q : kBad);
-    #pragma unroll
-                        for (uint32_t q = 0; q < 4; q++)
-                            if (k + 16 * q < L)
-                                lds_put(dst + k + 16 * q, v[q], min(16u, L - k - 16 * q));
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
-                    const int q = (int)__builtin_ctzll(lm);
-                    const uint32_t a = lane_val(op[j], q) - H, e = a + lane_val(L, q) - 1;
-                    for (uint32_t g = (a >> 5) + lane; g <= e >> 5; g += 64) {
-                        const uint32_t lo = g == a >> 5 ? a & 31 : 0, hi = g == e >> 5 ? e & 31 : 31;
-                        const uint32_t m = hi - lo == 31 ? 0xFFFFFFFFu : ((1u << (hi - lo + 1)) - 1) << lo;
-                        __hip_atomic_fetch_or(&done[g], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (!coop && L)
-                    mark(op[j] - H, L);
+                lit_runs_hbm(lsp, C + op[j] - H, src[j], L, lane);
+                mark_lit_runs(done, op[j] - H, L, lane);
                 pend[j] = on && ml[j] != 0;
             }
             {
                 const bool on0 = op[0] < lim && lit[0] + ml[0] != 0, on1 = op[1] < lim && lit[1] + ml[1] != 0;
-                const uint32_t e = max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u);
-                const uint32_t we = wave_incl_max(e);
-                if (lane == 63 && we)
-                    atomicMax(&hi_end, we);
+                note_end(&hi_end, max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u), lane);
             }
             __syncthreads();
             ZSK_BT(2)
-            for (uint32_t pass = 0;; pass++) {
-                bool moved = false;
-                for (int j = 0; j < 2; j++) {
-                    if (!pend[j])
-                        continue;
-                    const uint32_t mb = op[j] + lit[j], ov = off[j], m = ml[j];
-                    // the source's first min(off, ml) bytes: those before H are final
-                    const uint32_t s0 = mb - ov, s1 = s0 + (ov >= m ? m : ov);
-                    if (s1 > H && !ready(s0 > H ? s0 - H : 0u, s1 - (s0 > H ? s0 : H)))
-                        continue;
-                    const uint32_t db = C + mb - H, sb = db - ov;
-                    if (ov >= m && m <= 128) {
-                        scopy(db, sb, min(m, 64u));
-                        if (m > 64)
-                            scopy(db + 64, sb + 64, m - 64);
-                    } else if (ov >= m || ov >= 16) {
-                        lcopy(db, sb, m, ov >= m ? 64u : min(64u, ov & ~15u));
-                    } else {
-                        const uint32_t e = ov * ((16 + ov - 1) / ov);
-                        const uint32_t h = min(e, m);
-                        for (uint32_t k = 0; k < h; k++) {
-                            *lp<uint8_t>(db + k) = *lp<uint8_t>(sb + k);
-                            wave_lds_sync();
-                        }
-                        for (uint32_t k = h; k < m; k += 16) {
-                            lds_put(db + k, lds16(db + k - e), min(16u, m - k));
-                            wave_lds_sync();
-                        }
-                    }
-                    mark(mb - H, m);
-                    pend[j] = false;
-                    moved = true;
-                }
-                if (!__any(pend[0] || pend[1]) || pass > (1u << 22))
-                    break;
-                if (!__any(moved))
-                    __builtin_amdgcn_s_sleep(1);
-            }
+            match_passes(pend, [&](int j, bool pending) -> bool {
+                if (!pending)
+                    return false;
+                const uint32_t mb = op[j] + lit[j], ov = off[j], m = ml[j];
+                // the source's first min(off, ml) bytes: those before H are final
+                const uint32_t s0 = mb - ov, s1 = s0 + (ov >= m ? m : ov);
+                if (s1 > H && !ready_bytes(done, s0 > H ? s0 - H : 0u, s1 - (s0 > H ? s0 : H)))
+                    return false;
+                copy_match(C + mb - H, ov, m);
+                mark_bytes(done, mb - H, m);
+                return true;
+            });
             __syncthreads();
             ZSK_BT(3)
             const uint32_t P1 = ci != 0xFFFFFFFFu ? min(cut_op, P + tot[0] + tot[1]) : P + tot[0] + tot[1];
@@ -740,7 +765,7 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
             // slide once the window is cut or three quarters full (and there is
             // more to decode): its bytes out, the 64 KiB before P down as history
             if ((ci != 0xFFFFFFFFu || P - H >= kBWin - kBWin / 4) && w0 < nit && P < stop) {
-                put_out(H, H, P);
+                put_out(o, H, C, P - H, t);
                 const uint32_t sh = P - H;
                 u32x4 v[4];
     #pragma unroll
@@ -760,7 +785,8 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
         }
         if (stuck)
             return false;
-        put_out(H, H, min(hi_end, d.d_size));
+        const uint32_t E = min(hi_end, d.d_size);
+        put_out(o, H, C, E > H ? E - H : 0u, t);   // (nothing past H: no store)
 #ifdef ZSK_TUNING
         __syncthreads();
         ZSK_BT(5)
@@ -786,8 +812,9 @@ __global__ __launch_bounds__(kFT) void seq_exec_big_kernel(
 // blocks at once.  A block's matches may read up to 64 KiB back, i.e. the
 // previous block's output, which its own workgroup is still producing; so:
 //   A. every workgroup executes its block at once with the previous block's
-//      bytes unknown: the frame kernel's literal copies and match passes over
-//      the block staged in LDS (block byte x at B + x).  A byte copied from
+//      bytes unknown: the shared literal copies (lit_runs_hbm) and match
+//      passes (match_passes) over the block staged in LDS (block byte x at
+//      B + x).  A byte copied from
 //      before the block, or from a byte so copied, is *tainted* (a bit per
 //      byte): it holds not its value but its *origin*, the previous block's
 //      byte it is a copy of, low byte at B + x and high byte at B - 64 KiB + x
@@ -837,7 +864,7 @@ __global__ __launch_bounds__(kFT) void seq_exec_blocks_kernel(
     __shared__ uint32_t taint[kBWin / 32 + 2];
     __shared__ uint32_t wsum[kFT / 64];
     __shared__ uint32_t ntm, hi_end;
-    const uint32_t j = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t j = blockIdx.x, t = threadIdx.x, lane = t & 63;
     if (j >= (uint32_t)__builtin_amdgcn_readfirstlane(*njobs))
         return;
     const BlockJob J = jobs[j];
@@ -874,77 +901,9 @@ __global__ __launch_bounds__(kFT) void seq_exec_blocks_kernel(
     }
     __syncthreads();
 
-    auto scan = [&](uint32_t v, uint32_t &total) -> uint32_t {   // exclusive, in thread order
-        const uint32_t inc = wave_incl_add(v);
-        if (lane == 63)
-            wsum[wv] = inc;
-        __syncthreads();
-        uint32_t before = 0, tot = 0;
-        for (uint32_t k = 0; k < kFT / 64; k++) {
-            const uint32_t x = wsum[k];
-            before += k < wv ? x : 0;
-            tot += x;
-        }
-        __syncthreads();
-        total = tot;
-        return before + inc - v;
-    };
-    auto bits_or = [&](uint32_t *w, uint32_t a, uint32_t len) {
-        for (const uint32_t e = a + len; a < e;) {
-            const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-            __hip_atomic_fetch_or(&w[a >> 5], nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0, __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_WORKGROUP);
-            a += nb;
-        }
-    };
-    auto all_set = [&](uint32_t *w, uint32_t a, uint32_t len) -> bool {
-        bool all = true;
-        for (const uint32_t e = a + len; a < e;) {
-            const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-            const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
-            all &= (__hip_atomic_load(&w[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) == m;
-            a += nb;
-        }
-        return all;
-    };
-    auto any_set = [&](uint32_t *w, uint32_t a, uint32_t len) -> bool {
-        bool any = false;
-        for (const uint32_t e = a + len; a < e;) {
-            const uint32_t b0 = a & 31, nb = min(32 - b0, e - a);
-            const uint32_t m = nb == 32 ? 0xFFFFFFFFu : ((1u << nb) - 1) << b0;
-            any |= (__hip_atomic_load(&w[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & m) != 0;
-            a += nb;
-        }
-        return any;
-    };
-    auto mark = [&](uint32_t a, uint32_t len) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        bits_or(done, a, len);
-    };
-    // a match reading no tainted byte: a plain copy inside the staged block
-    auto copy_match = [&](uint32_t mb, uint32_t ov, uint32_t m) {
-        const uint32_t db = B + mb, sb = db - ov;
-        if (ov >= m && m <= 128) {
-            scopy(db, sb, min(m, 64u));
-            if (m > 64)
-                scopy(db + 64, sb + 64, m - 64);
-        } else if (ov >= m || ov >= 16) {
-            lcopy(db, sb, m, ov >= m ? 64u : min(64u, ov & ~15u));
-        } else {
-            const uint32_t e = ov * ((16 + ov - 1) / ov);
-            const uint32_t h = min(e, m);
-            for (uint32_t k = 0; k < h; k++) {
-                *lp<uint8_t>(db + k) = *lp<uint8_t>(sb + k);
-                wave_lds_sync();
-            }
-            for (uint32_t k = h; k < m; k += 16) {
-                lds_put(db + k, lds16(db + k - e), min(16u, m - k));
-                wave_lds_sync();
-            }
-        }
-    };
-    // one that does: the wave's 64 lanes a byte each, byte k's source
-    // s = mb - ov + k mod ov (before the match, so the bytes are independent;
+    // a match reading no tainted byte is a plain copy inside the staged block
+    // (copy_match).  One that does: the wave's 64 lanes a byte each, byte k's
+    // source s = mb - ov + k mod ov (before the match, so the bytes are independent;
     // an overlapping match repeats its first ov source bytes), a byte before
     // the block becoming the origin s + 64 KiB, a tainted one passing its
     // origin on, an untainted one its value; the taint bits of 64 bytes at a
@@ -1048,116 +1007,56 @@ __global__ __launch_bounds__(kFT) void seq_exec_blocks_kernel(
         for (uint32_t w0 = 0; w0 < nit && P < lim; w0 += 2 * kFT) {
             uint32_t lit[2], ml[2], off[2], src[2], op[2], tot[2];
             for (int q = 0; q < 2; q++) {
-                const uint32_t i = w0 + q * kFT + t;
-                lit[q] = ml[q] = off[q] = src[q] = 0;
-                if (i < nit) {
-                    const uint64_t cur = it[i];
-                    const uint32_t c0 = (uint32_t)cur, c1 = (uint32_t)(cur >> 32);
-                    const bool second = i > 0 && ((uint32_t)it[i - 1] & kItemExt);
-                    if (!second) {
-                        src[q] = c0 & kItemPos;
-                        if (c0 & kItemExt) {
-                            const uint64_t nx = it[i + 1];
-                            lit[q] = (uint32_t)nx;
-                            ml[q] = (uint32_t)(nx >> 32);
-                            off[q] = c1;
-                        } else {
-                            lit[q] = (c1 >> 16) & 0xFF;
-                            const uint32_t mc = c1 >> 24;
-                            ml[q] = mc ? mc + 3 : 0;
-                            off[q] = c1 & 0xFFFF;
-                        }
-                    }
-                }
+                const Seq s = load_seq(it, w0 + q * kFT + t, nit, SameSlot{});
+                lit[q] = s.lit, ml[q] = s.ml, off[q] = s.off, src[q] = s.src;
             }
-            const uint32_t x0 = scan(lit[0] + ml[0], tot[0]);
-            const uint32_t x1 = scan(lit[1] + ml[1], tot[1]);
+            const uint32_t x0 = wg_scan(lit[0] + ml[0], tot[0], wsum);
+            const uint32_t x1 = wg_scan(lit[1] + ml[1], tot[1], wsum);
             op[0] = P + x0;
             op[1] = P + tot[0] + x1;
             bool pend[2];
             for (int q = 0; q < 2; q++) {
                 const bool on = op[q] < lim && lit[q] + ml[q] != 0 && op[q] + lit[q] + ml[q] <= kBWin;
                 const uint32_t L = on ? lit[q] : 0;
-                const uint32_t dst = B + op[q];
-                const bool coop = L > kFLong;
-                for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
-                    const int qq = (int)__builtin_ctzll(lm);
-                    const uint32_t d0 = lane_val(dst, qq), sx = lane_val(src[q], qq), nq = lane_val(L, qq);
-                    for (uint32_t k = 16 * lane; k < nq; k += 1024)
-                        lds_put(d0 + k, load16u(lsp.r, lsp.s0 + sx + k), min(16u, nq - k));
-                }
-                if (!coop && L) {
-                    for (uint32_t k = 0; k < L; k += 64) {
-                        u32x4 v[4];
-#pragma unroll
-                        for (uint32_t qq = 0; qq < 4; qq++)
-                            v[qq] = load16u(lsp.r, k + 16 * qq < L ? lsp.s0 + src[q] + k + 16 * qq : kBad);
-#pragma unroll
-                        for (uint32_t qq = 0; qq < 4; qq++)
-                            if (k + 16 * qq < L)
-                                lds_put(dst + k + 16 * qq, v[qq], min(16u, L - k - 16 * qq));
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                for (uint64_t lm = __ballot(coop); lm; lm &= lm - 1) {
-                    const int qq = (int)__builtin_ctzll(lm);
-                    const uint32_t a = lane_val(op[q], qq), e = a + lane_val(L, qq) - 1;
-                    for (uint32_t g = (a >> 5) + lane; g <= e >> 5; g += 64) {
-                        const uint32_t lo = g == a >> 5 ? a & 31 : 0, hi = g == e >> 5 ? e & 31 : 31;
-                        const uint32_t m = hi - lo == 31 ? 0xFFFFFFFFu : ((1u << (hi - lo + 1)) - 1) << lo;
-                        __hip_atomic_fetch_or(&done[g], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (!coop && L)
-                    mark(op[q], L);
+                lit_runs_hbm(lsp, B + op[q], src[q], L, lane);
+                mark_lit_runs(done, op[q], L, lane);
                 pend[q] = on && ml[q] != 0;
             }
             {
                 const bool on0 = op[0] < lim && lit[0] + ml[0] != 0, on1 = op[1] < lim && lit[1] + ml[1] != 0;
-                const uint32_t e = max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u);
-                const uint32_t we = wave_incl_max(e);
-                if (lane == 63 && we)
-                    atomicMax(&hi_end, we);
+                note_end(&hi_end, max(on0 ? op[0] + lit[0] + ml[0] : 0u, on1 ? op[1] + lit[1] + ml[1] : 0u), lane);
             }
             __syncthreads();
-            for (uint32_t pass = 0;; pass++) {
-                bool moved = false;
-                for (int q = 0; q < 2; q++) {
-                    const uint32_t mb = op[q] + lit[q], ov = off[q], m = ml[q];
-                    bool rdy = false, tnt = false;
-                    if (pend[q]) {
-                        uint32_t a, len;
-                        const bool before = src_range(mb, ov, m, a, len);
-                        rdy = !len || all_set(done, a, len);
-                        if (rdy) {
-                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                            tnt = before || (len && any_set(taint, a, len));
-                        }
-                    }
-                    // tainted: short offsets and long matches with the
-                    // wave's lanes a byte each, the others by their lane
-                    const bool wide = rdy && tnt && (ov < 16 || m > 256);
-                    for (uint64_t lm = __ballot(wide); lm; lm &= lm - 1) {
-                        const int qq = (int)__builtin_ctzll(lm);
-                        taint_wide(lane_val(mb, qq), lane_val(ov, qq), lane_val(m, qq));
-                    }
-                    if (rdy && tnt && !wide)
-                        taint_copy(mb, ov, m);
-                    if (rdy && !tnt)
-                        copy_match(mb, ov, m);
+            match_passes(pend, [&](int q, bool pending) -> bool {
+                const uint32_t mb = op[q] + lit[q], ov = off[q], m = ml[q];
+                bool rdy = false, tnt = false;
+                if (pending) {
+                    uint32_t a, len;
+                    const bool before = src_range(mb, ov, m, a, len);
+                    rdy = !len || all_set(done, a, len);
                     if (rdy) {
-                        if (tnt)
-                            atomicAdd(&ntm, 1u);
-                        mark(mb, m);
-                        pend[q] = false;
-                        moved = true;
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                        tnt = before || (len && any_set(taint, a, len));
                     }
                 }
-                if (!__any(pend[0] || pend[1]) || pass > (1u << 22))
-                    break;
-                if (!__any(moved))
-                    __builtin_amdgcn_s_sleep(1);
-            }
+                // tainted: short offsets and long matches with the
+                // wave's lanes a byte each, the others by their lane
+                const bool wide = rdy && tnt && (ov < 16 || m > 256);
+                for (uint64_t lm = __ballot(wide); lm; lm &= lm - 1) {
+                    const int qq = (int)__builtin_ctzll(lm);
+                    taint_wide(lane_val(mb, qq), lane_val(ov, qq), lane_val(m, qq));
+                }
+                if (rdy && tnt && !wide)
+                    taint_copy(mb, ov, m);
+                if (rdy && !tnt)
+                    copy_match(B + mb, ov, m);
+                if (rdy) {
+                    if (tnt)
+                        atomicAdd(&ntm, 1u);
+                    mark_bytes(done, mb, m);
+                }
+                return rdy;
+            });
             __syncthreads();
             P += tot[0] + tot[1];
         }
@@ -1167,19 +1066,11 @@ __global__ __launch_bounds__(kFT) void seq_exec_blocks_kernel(
     ZSK_KT(1)
 
     // ---- phase B: the block's bytes [0, E) out at once (the tainted ones
-    // holding origins yet): a byte head to 16-byte alignment, whole 16-byte
-    // stores, a byte tail; its taint bits and (with tainted bytes) its
-    // origins to the job's scratch; then published ----
+    // holding origins yet, put_out); its taint bits and (with tainted bytes)
+    // its origins to the job's scratch; then published ----
     const uint32_t E = min(hi_end, lim);
     uint8_t *o = out + d.d_off + bop;
-    const uint32_t head = min(E, (uint32_t)((16 - ((uintptr_t)o & 15)) & 15));
-    const uint32_t nchunks = (E - head) / 16, tail0 = head + 16 * nchunks;
-    if (t < head)
-        o[t] = ob[kBWin + t];
-    for (uint32_t c = t; c < nchunks; c += kFT)
-        *reinterpret_cast<u32x4 *>(o + head + 16 * c) = lds16(B + head + 16 * c);
-    if (tail0 + t < E)
-        o[tail0 + t] = ob[kBWin + tail0 + t];
+    put_out(o, 0, B, E, t);
     for (uint32_t i = t; i < kBWin / 32; i += kFT)
         btaint[(size_t)j * (kBWin / 32) + i] = taint[i];
     if (nt) {
@@ -1209,7 +1100,7 @@ __global__ __launch_bounds__(kFT) void seq_exec_blocks_kernel(
         // taint words' prefix counts (in done[], dead now)
         const uint32_t c0 = __builtin_popcount(taint[2 * t]), c1 = __builtin_popcount(taint[2 * t + 1]);
         uint32_t T;
-        const uint32_t pre = scan(c0 + c1, T);
+        const uint32_t pre = wg_scan(c0 + c1, T, wsum);
         done[2 * t] = pre;
         done[2 * t + 1] = pre + c0;
         __syncthreads();
