@@ -64,7 +64,10 @@ typedef enum {
     ZSEEK_LZ4,
 } zseek_compression_type_t;
 
-/* zstd writer controls (ref zseek.h:129-140). */
+/* zstd writer controls (ref zseek.h:129-140).  nb_workers > 1 streams each
+ * frame through ZSTD_compressStream2 on that many libzstd worker threads;
+ * with a libzstd built without multithreading the same frames are streamed
+ * on the calling thread (the reference fails to open there). */
 typedef struct {
     int nb_workers;
     size_t cpusetsize;

@@ -30,6 +30,14 @@
  *                            (compress.c:750 direct frames, :483 buffered
  *                            ones; prefs compress.c:203-207), batched over
  *                            frames of <= 4 MiB in one grid.
+ *   zsk_frame_checksums, zsk_writer_set_checksums — the seek table's
+ *                            per-frame checksum on the writing side
+ *                            (ZSTD_seekable_logFrame's XXH64 and the 12-byte
+ *                            entries of seek_table.c:374-407, which the
+ *                            reference's writer never turns on), hashed on
+ *                            the GPU for frames that are compressed there.
+ *   zsk_write_device       — zseek_write (compress.c:650-833) for bytes that
+ *                            are already in device memory.
  */
 #ifndef ZSEEK_HIP_H
 #define ZSEEK_HIP_H
@@ -283,6 +291,14 @@ ZSEEK_EXPORT int zsk_verify_frame_checksums(const zsk_frame_desc_t *d_desc,
     uint32_t nframes, const void *d_out, const uint32_t *d_checksums,
     int32_t *d_status, void *stream);
 
+/* The compute form of the same hash:
+ * d_checksums[f] = low 32 bits of XXH64(seed 0) of d_data[d_off, d_off + d_size)
+ * for each of the nframes descriptors (c_off / c_size ignored).  d_size 0 is
+ * valid (0x51D8E999).  Reads nothing outside a frame's bytes; writes exactly
+ * d_checksums[0, nframes).  Asynchronous on stream; 0 or -1; nframes == 0: 0. */
+ZSEEK_EXPORT int zsk_frame_checksums(const zsk_frame_desc_t *d_desc, uint32_t nframes,
+    const void *d_data, uint32_t *d_checksums, void *stream);
+
 /* Make a reader check the seek-table checksum of every frame it decodes
  * (files whose seek table carries them).  Default off, as the reference; env
  * ZSEEK_VERIFY_CHECKSUMS=1 at open turns it on.  A mismatching frame fails
@@ -381,6 +397,41 @@ ZSEEK_EXPORT int zsk_lz4_compress_frames(const zsk_compress_desc_t *d_desc,
  * writer, an HC level (>= 3) or no HIP device.
  */
 ZSEEK_EXPORT bool zsk_writer_set_gpu_compress(zseek_writer_t *writer, size_t batch_bytes);
+
+/* Make the file's seek table carry per-frame checksums (descriptor bit 7,
+ * 12-byte entries cSize, dSize, checksum: seek_table.c:374-407 of the
+ * reference).  Only before anything has been written: false once a frame
+ * has been logged or queued or bytes are buffered (and for NULL).  Setting
+ * the value it already has returns true.  Env ZSEEK_WRITE_CHECKSUMS=1 at
+ * open.  Default off: files are then byte for byte what they are without
+ * this call.  Frames compressed on the host are hashed there; a GPU-mode
+ * batch is hashed on the GPU, on the compression's stream.  With checksums
+ * on, zseek_writer_stats counts 12 bytes per frame in seek_table_size and
+ * compressed_size (the reference's stats always assume 8). */
+ZSEEK_EXPORT bool zsk_writer_set_checksums(zseek_writer_t *writer, bool on);
+
+/* The bytes d_buf[0, len) (device memory of the writer's GPU-mode device, or
+ * of the calling thread's current device when GPU mode is off) written as if
+ * they were host memory and the caller had run
+ *     for (o = 0; o < len; o += write_size)
+ *         if (!zseek_write(w, host + o, min(write_size, len - o), call_data, errbuf)) return false;
+ * (write_size 0: one write of len; len 0: one empty write).  The file, the
+ * frames, each write callback's bytes and call_data, and the stats afterwards
+ * are exactly that loop's.  Synchronous: the call returns with nothing queued
+ * (it flushes what earlier zseek_write calls queued, in order, then its own
+ * frames), so a compression or callback failure of its frames is reported by
+ * this call; d_buf may be reused on return.  The bytes must be complete when
+ * the call is made (the work that produced them synchronized).
+ * In GPU mode, with nothing buffered and min_frame_size <= write_size <=
+ * 4 MiB, the pieces are compressed (and hashed) where they are and only
+ * compressed frames cross to the host; every other case (zstd, GPU mode off,
+ * other piece sizes, bytes already buffered) downloads the pieces and takes
+ * zseek_write's path.
+ * false + errbuf for a NULL writer ("invalid writer"), a pointer that is not
+ * device memory of that device ("write from device: not device memory of the
+ * writer's device"), and everything zseek_write fails on. */
+ZSEEK_EXPORT bool zsk_write_device(zseek_writer_t *writer, const void *d_buf, size_t len,
+    size_t write_size, void *call_data, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 #ifdef __cplusplus
 }

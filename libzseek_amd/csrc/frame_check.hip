@@ -1,4 +1,5 @@
-// frame_check.hip — seek-table frame checksums verified on the GPU (gfx950).
+// frame_check.hip — seek-table frame checksums verified and computed on the
+// GPU (gfx950).
 //
 // The seekable format's per-frame checksum (descriptor bit 7) is the low 32
 // bits of XXH64(seed 0) of the frame's decompressed bytes; the reference
@@ -13,7 +14,13 @@
 // loads are issued before the dependent rounds.  The tail (< 32 bytes) and
 // the avalanche run on the frame's lane 0, serially, as XXH64 defines them.
 // Algorithmic bytes per frame: d_size read once.
+//
+// The writer needs the same hash the other way round: the checksum of each
+// frame it compresses, stored instead of compared (zsk_frame_checksums, and
+// launch_src_checksums over the compressor's descriptors).  Both kernels call
+// one frame_xxh64 body.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/zseek_hip.h"
@@ -54,22 +61,14 @@ __device__ __forceinline__ uint64_t ld8(const uint8_t *p)
     return *reinterpret_cast<const u64_ua *>(p);
 }
 
-__global__ __launch_bounds__(256) void frame_xxh64_kernel(const FrameDesc *__restrict__ desc, uint32_t n,
-                                                          const uint8_t *__restrict__ out,
-                                                          const uint32_t *__restrict__ want,
-                                                          int32_t *__restrict__ status)
+// XXH64(seed 0) of p[0, len), low 32 bits, by the frame's four lanes (k =
+// 0..3, consecutive lanes of one wave; every lane of the wave calls this, a
+// lane with on == false passes len 0 and reads nothing).  The frame's lane 0
+// hands the result to sink(h32); the other lanes return without one.  The one
+// XXH64 body: the verify and compute kernels differ only in their sink.
+template <typename Sink>
+__device__ __forceinline__ void frame_xxh64(const uint8_t *p, uint32_t len, bool on, uint32_t k, Sink sink)
 {
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t f = t >> 2, k = t & 3;
-    // the four lanes of a frame agree on `on`: they read the same status
-    const bool on = f < n && status[f] == ST_OK;
-    uint32_t len = 0;
-    const uint8_t *p = out;
-    if (on) {
-        const FrameDesc d = desc[f];
-        len = d.d_size;
-        p = out + d.d_off;
-    }
     const uint32_t stripes = len / 32;
     uint64_t acc = k == 0 ? P1 + P2 : k == 1 ? P2 : k == 2 ? 0 : 0ull - P1;
     const uint8_t *q = p + 8 * k;
@@ -120,8 +119,61 @@ __global__ __launch_bounds__(256) void frame_xxh64_kernel(const FrameDesc *__res
     h ^= h >> 29;
     h *= P3;
     h ^= h >> 32;
-    if ((uint32_t)h != want[f])
-        status[f] = ST_SEEK_CHECKSUM;
+    sink((uint32_t)h);
+}
+
+__global__ __launch_bounds__(256) void frame_xxh64_kernel(const FrameDesc *__restrict__ desc, uint32_t n,
+                                                          const uint8_t *__restrict__ out,
+                                                          const uint32_t *__restrict__ want,
+                                                          int32_t *__restrict__ status)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t f = t >> 2, k = t & 3;
+    // the four lanes of a frame agree on `on`: they read the same status
+    const bool on = f < n && status[f] == ST_OK;
+    uint32_t len = 0;
+    const uint8_t *p = out;
+    if (on) {
+        const FrameDesc d = desc[f];
+        len = d.d_size;
+        p = out + d.d_off;
+    }
+    frame_xxh64(p, len, on, k, [&](uint32_t h) {
+        if (h != want[f])
+            status[f] = ST_SEEK_CHECKSUM;
+    });
+}
+
+// The compute form: sums[f] = the checksum of data[off_f, off_f + size_f),
+// the u64 offset and u32 size of frame f read at `stride` bytes per frame from
+// off0 / size0 (zsk_frame_desc_t's d_off / d_size, or zsk_compress_desc_t's
+// src_off / src_size: no descriptors are repacked for it).
+__global__ __launch_bounds__(256) void frame_xxh64_store_kernel(const uint8_t *__restrict__ off0,
+                                                                const uint8_t *__restrict__ size0, uint32_t stride,
+                                                                uint32_t n, const uint8_t *__restrict__ data,
+                                                                uint32_t *__restrict__ sums)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t f = t >> 2, k = t & 3;
+    const bool on = f < n;
+    uint32_t len = 0;
+    const uint8_t *p = data;
+    if (on) {
+        len = *reinterpret_cast<const uint32_t *>(size0 + (size_t)f * stride);
+        p = data + *reinterpret_cast<const uint64_t *>(off0 + (size_t)f * stride);
+    }
+    frame_xxh64(p, len, on, k, [&](uint32_t h) { sums[f] = h; });
+}
+
+int launch_store(const uint8_t *off0, const uint8_t *size0, uint32_t stride, uint32_t nframes, const uint8_t *d_data,
+                 uint32_t *d_sums, hipStream_t stream)
+{
+    if (!d_sums)
+        return -1;
+    const uint32_t blocks = (uint32_t)(((uint64_t)nframes * 4 + 255) / 256);
+    hipLaunchKernelGGL(frame_xxh64_store_kernel, dim3(blocks), dim3(256), 0, stream, off0, size0, stride, nframes,
+                       d_data, d_sums);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }   // namespace
@@ -137,7 +189,39 @@ int launch_frame_checksums(const FrameDesc *d_desc, uint32_t nframes, const uint
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+int launch_frame_checksums_compute(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_data,
+                                   uint32_t *d_sums, hipStream_t stream)
+{
+    if (nframes == 0)
+        return 0;
+    if (!d_desc)
+        return -1;
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(d_desc);
+    return launch_store(b + offsetof(FrameDesc, d_off), b + offsetof(FrameDesc, d_size), sizeof(FrameDesc), nframes,
+                        d_data, d_sums, stream);
+}
+
+int launch_src_checksums(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src,
+                         uint32_t *d_sums, hipStream_t stream)
+{
+    if (nframes == 0)
+        return 0;
+    if (!d_desc)
+        return -1;
+    const uint8_t *b = reinterpret_cast<const uint8_t *>(d_desc);
+    return launch_store(b + offsetof(zsk_compress_desc_t, src_off), b + offsetof(zsk_compress_desc_t, src_size),
+                        sizeof(zsk_compress_desc_t), nframes, d_src, d_sums, stream);
+}
+
 }   // namespace zsk
+
+extern "C" ZSEEK_EXPORT int zsk_frame_checksums(const zsk_frame_desc_t *d_desc, uint32_t nframes, const void *d_data,
+                                                uint32_t *d_checksums, void *stream)
+{
+    return zsk::launch_frame_checksums_compute(reinterpret_cast<const zsk::FrameDesc *>(d_desc), nframes,
+                                               static_cast<const uint8_t *>(d_data), d_checksums,
+                                               static_cast<hipStream_t>(stream));
+}
 
 extern "C" ZSEEK_EXPORT int zsk_verify_frame_checksums(const zsk_frame_desc_t *d_desc, uint32_t nframes,
                                                        const void *d_out, const uint32_t *d_checksums,

@@ -23,6 +23,10 @@
 //                           (ours, or the reference build in oracle/_ref):
 //                           both share the zseek.h ABI, so the same callback
 //                           and the same timing loop serve both sides.
+//   zsk_tool_sink_write     a writer's in-memory sink with a C write callback
+//                           (memcpy into a caller-owned buffer): user_data is
+//                           a zsk_tool_sink_t {buf, cap, used}; a write past
+//                           cap is refused (scripts/writer_probe.py).
 //   zsk_tool_latency        per-request wall time of `count`-byte reads at
 //                           given offsets (a request loops on short reads, as
 //                           test/example.c:63-80 does).
@@ -376,6 +380,21 @@ ZSK_TOOL bool zsk_tool_close_mem(void *close_fn, void *reader)
         g_mem.erase(it);
     }
     return ok;
+}
+
+struct zsk_tool_sink_t {
+    uint8_t *buf;
+    size_t cap, used;
+};
+
+ZSK_TOOL bool zsk_tool_sink_write(const void *data, size_t size, void *user_data, void *)
+{
+    zsk_tool_sink_t *s = (zsk_tool_sink_t *)user_data;
+    if (size > s->cap - s->used)
+        return false;
+    memcpy(s->buf + s->used, data, size);
+    s->used += size;
+    return true;
 }
 
 // ns_out[i] = wall time of request i; returns 0, or -1 at the first failing

@@ -17,6 +17,17 @@
 // LZ4F_compressFrame) and then written and logged in queue order, each with
 // the call_data of the zseek_write that produced it.  Frames the GPU path
 // does not take flush the queue first, so the file is the same byte for byte.
+//
+// Seek-table checksums (zsk_writer_set_checksums, env ZSEEK_WRITE_CHECKSUMS):
+// each logged frame carries the low 32 bits of XXH64 of its uncompressed
+// bytes, hashed where the bytes are -- on the host (xxh64_host.h) for frames
+// compressed there, on the GPU (launch_src_checksums, the compression's
+// stream) for a GPU batch -- and close writes 12-byte entries, descriptor 0x80.
+//
+// zsk_write_device: the caller's bytes are in device memory.  In GPU mode
+// whole pieces are compressed (and hashed) straight out of the caller's
+// buffer; everything else comes down through a pinned bounce and takes
+// zseek_write's path.
 #include <errno.h>
 #include <pthread.h>
 #include <stdint.h>
@@ -30,10 +41,12 @@
 #include <hip/hip_runtime.h>
 #include <lz4frame.h>
 #include <zstd.h>
+#include <zstd_errors.h>
 
 #include "../../include/zseek.h"
 #include "../../include/zseek_hip.h"
 #include "host.h"
+#include "xxh64_host.h"
 
 using namespace zsk;
 
@@ -41,7 +54,7 @@ namespace {
 constexpr uint32_t kMaxFrames = 0x8000000u;   // ZSTD_SEEKABLE_MAXFRAMES (ref seek_table.c:17)
 
 struct FrameLogEntry {
-    uint32_t c_size, d_size;
+    uint32_t c_size, d_size, checksum;
 };
 
 constexpr size_t kGpuDefaultBatch = 1u << 30;   // 16,384 frames of 64 KiB: ~20 GB/s per launch (bench launch_by_frames)
@@ -50,6 +63,14 @@ constexpr size_t kGpuMinBatch = 65536;   // smallest batch: one 64 KiB frame
 constexpr size_t kGpuMaxBatchFrames = 65536;
 constexpr size_t kGpuTableBytes = 65536;      // compressor scratch per queued frame
 constexpr size_t kGpuFirstStaging = 64u << 20;   // staging starts here, grows x2 to the batch
+// zsk_write_device, frames of <= 64 KiB: most input bytes per launch.  1 GiB
+// written from device memory ran at 4.5 / 7.4 / 4.8 GB/s with 64 MiB / 256 MiB
+// / 1 GiB batches: wider launches against the bigger pinned output staging's
+// allocation.  Linked frames (> 64 KiB) take batch_bytes, as in gpu_queue: a
+// launch of them costs about one frame's chain whatever it holds (1 MiB
+// frames 0.67 / 2.3 / 3.8-4.6 GB/s)
+constexpr size_t kGpuDeviceBatch = 256u << 20;
+constexpr size_t kBouncePiece = 4u << 20;        // zsk_write_device's host path: bytes per download
 
 // Queued LZ4 frames of a writer in GPU mode and the buffers they go through.
 struct GpuLz4 {
@@ -62,7 +83,7 @@ struct GpuLz4 {
     size_t in_cap = 0, out_cap = 0, in_used = 0, out_used = 0;
     uint8_t *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
     zsk_compress_desc_t *d_desc = nullptr;
-    uint32_t *d_csize = nullptr;
+    uint32_t *d_csize = nullptr;   // 2 x d_frames words: frame sizes, then checksums
     size_t d_frames = 0, d_scratch_cap = 0;
     std::vector<zsk_compress_desc_t> desc;
     std::vector<uint32_t> csize;
@@ -93,7 +114,7 @@ struct GpuLz4 {
     {
         // (the first staging is allocated even for an empty frame: its output
         // slot needs room although it has no input bytes)
-        if (in_need <= in_cap && out_cap)
+        if (in_need <= in_cap && in_cap && out_cap)
             return true;
         size_t cap = in_cap ? in_cap : kGpuFirstStaging;
         while (cap < in_need)
@@ -119,6 +140,28 @@ struct GpuLz4 {
         out_cap = ocap;
         return true;
     }
+
+    // the output side alone (zsk_write_device's frames are read where the
+    // caller has them: no input staging), nothing queued
+    bool reserve_out(size_t out_need)
+    {
+        if (out_need <= out_cap)
+            return true;
+        size_t cap = out_cap ? out_cap : out_need;
+        while (cap < out_need)
+            cap *= 2;
+        if (d_out)
+            (void)hipFree(d_out);
+        if (h_out)
+            (void)hipHostFree(h_out);
+        d_out = h_out = nullptr;
+        out_cap = 0;
+        if (hipHostMalloc((void **)&h_out, cap, hipHostMallocDefault) != hipSuccess ||
+            hipMalloc((void **)&d_out, cap) != hipSuccess)
+            return false;
+        out_cap = cap;
+        return true;
+    }
 };
 }   // namespace
 
@@ -135,6 +178,11 @@ struct zseek_writer {
     std::vector<FrameLogEntry> log;
     std::vector<uint8_t> ubuf, cbuf;
     GpuLz4 gpu;
+    bool checksums = false;   // the seek table carries per-frame checksums
+    uint32_t frame_ck = 0;    // current frame's checksum, set by whoever hashed it
+    Xxh64 hash;               // multi-worker zstd: the frame's bytes arrive over several writes
+    uint8_t *bounce = nullptr;   // zsk_write_device's pinned download buffer
+    size_t bounce_cap = 0;
 };
 
 static bool default_write(const void *data, size_t size, void *user_data, void *call_data)
@@ -149,10 +197,13 @@ static bool log_frame(zseek_writer *w, char *errbuf)
         set_error(errbuf, "log frame: Frame index is too large");
         return false;
     }
-    w->log.push_back(FrameLogEntry{(uint32_t)w->frame_cm, (uint32_t)w->frame_uc});
+    w->log.push_back(FrameLogEntry{(uint32_t)w->frame_cm, (uint32_t)w->frame_uc, w->frame_ck});
     w->total_cm += w->frame_cm;
     w->frame_uc = 0;
     w->frame_cm = 0;
+    w->frame_ck = 0;
+    if (w->checksums && w->mt)
+        w->hash.init();
     return true;
 }
 
@@ -165,17 +216,17 @@ static bool emit(zseek_writer *w, const void *p, size_t n, void *call_data, char
     return true;
 }
 
-// Compress the queued frames on the GPU, then write and log them in order.
-static bool gpu_flush(zseek_writer *w, char *errbuf)
+// Compress the frames desc describes in d_src (the writer's d_in after
+// uploading its first `upload` bytes from h_in, or a caller's device buffer)
+// on the GPU, hash them there when the seek table carries checksums, then
+// write and log them in order.  out_used: the bytes of d_out their slots
+// span.  cds: a call_data per frame, or NULL: `cd` for every frame.
+static bool gpu_batch(zseek_writer *w, const uint8_t *d_src, size_t upload,
+                      const std::vector<zsk_compress_desc_t> &desc, size_t out_used,
+                      const std::vector<void *> *cds, void *cd, char *errbuf)
 {
     GpuLz4 &g = w->gpu;
-    if (g.failed) {
-        set_error(errbuf, "%s: %s", "compress frame", "GPU compression failed");
-        return false;
-    }
-    const size_t n = g.desc.size();
-    if (n == 0)
-        return true;
+    const size_t n = desc.size();
     DeviceGuard keep;
     bool ok = hipSetDevice(g.device) == hipSuccess;
     if (ok && g.d_frames < n) {
@@ -187,7 +238,7 @@ static bool gpu_flush(zseek_writer *w, char *errbuf)
         g.d_csize = nullptr;
         g.d_frames = 0;
         ok = hipMalloc(&g.d_desc, n * sizeof(zsk_compress_desc_t)) == hipSuccess &&
-             hipMalloc(&g.d_csize, n * sizeof(uint32_t)) == hipSuccess;
+             hipMalloc(&g.d_csize, 2 * n * sizeof(uint32_t)) == hipSuccess;
         if (ok)
             g.d_frames = n;
     }
@@ -201,31 +252,29 @@ static bool gpu_flush(zseek_writer *w, char *errbuf)
         if (ok)
             g.d_scratch_cap = scratch;
     }
-    g.csize.resize(n);
-    ok = ok && hipMemcpyAsync(g.d_in, g.h_in, g.in_used, hipMemcpyHostToDevice, g.stream) == hipSuccess &&
-         hipMemcpyAsync(g.d_desc, g.desc.data(), n * sizeof(zsk_compress_desc_t), hipMemcpyHostToDevice,
+    // sizes in csize[0, n); with checksums on, the frames' checksums behind
+    // them in csize[n, 2n), one download for both
+    const size_t words = w->checksums ? 2 * n : n;
+    g.csize.resize(words);
+    ok = ok && (upload == 0 || hipMemcpyAsync(g.d_in, g.h_in, upload, hipMemcpyHostToDevice, g.stream) == hipSuccess) &&
+         hipMemcpyAsync(g.d_desc, desc.data(), n * sizeof(zsk_compress_desc_t), hipMemcpyHostToDevice,
                         g.stream) == hipSuccess &&
-         zsk_lz4_compress_frames(g.d_desc, (uint32_t)n, g.d_in, g.d_out, g.d_csize, w->prefs.compressionLevel,
+         zsk_lz4_compress_frames(g.d_desc, (uint32_t)n, d_src, g.d_out, g.d_csize, w->prefs.compressionLevel,
                                  g.d_scratch, g.stream) == 0 &&
-         hipMemcpyAsync(g.csize.data(), g.d_csize, n * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream) ==
+         (!w->checksums || launch_src_checksums(g.d_desc, (uint32_t)n, d_src, g.d_csize + n, g.stream) == 0) &&
+         hipMemcpyAsync(g.csize.data(), g.d_csize, words * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream) ==
              hipSuccess &&
-         hipMemcpyAsync(g.h_out, g.d_out, g.out_used, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+         hipMemcpyAsync(g.h_out, g.d_out, out_used, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
          hipStreamSynchronize(g.stream) == hipSuccess;
-    std::vector<zsk_compress_desc_t> desc;
-    std::vector<void *> cds;
-    desc.swap(g.desc);
-    cds.swap(g.call_data);
     if (!ok) {
         // copies already queued may still read the staging: drain the stream
         // before anything reuses it; the queued frames are lost, so the
         // writer stays failed (later writes and close return false)
         (void)hipStreamSynchronize(g.stream);
-        g.in_used = g.out_used = 0;
         g.failed = true;
         set_error(errbuf, "%s: %s", "compress frame", "GPU compression failed");
         return false;
     }
-    g.in_used = g.out_used = 0;
     // the frame being buffered (ubuf) keeps its counters across the flush
     const size_t uc = w->frame_uc, cm = w->frame_cm;
     for (size_t f = 0; f < n && ok; f++) {
@@ -236,13 +285,34 @@ static bool gpu_flush(zseek_writer *w, char *errbuf)
         }
         w->frame_uc = desc[f].src_size;
         w->frame_cm = g.csize[f];
-        ok = emit(w, g.h_out + desc[f].dst_off, g.csize[f], cds[f], errbuf) && log_frame(w, errbuf);
+        w->frame_ck = w->checksums ? g.csize[n + f] : 0;
+        ok = emit(w, g.h_out + desc[f].dst_off, g.csize[f], cds ? (*cds)[f] : cd, errbuf) && log_frame(w, errbuf);
     }
     w->frame_uc = uc;
     w->frame_cm = cm;
+    w->frame_ck = 0;
     if (!ok)   // frames after the failing one are not in the file
         g.failed = true;
     return ok;
+}
+
+// Compress the queued frames on the GPU, then write and log them in order.
+static bool gpu_flush(zseek_writer *w, char *errbuf)
+{
+    GpuLz4 &g = w->gpu;
+    if (g.failed) {
+        set_error(errbuf, "%s: %s", "compress frame", "GPU compression failed");
+        return false;
+    }
+    if (g.desc.empty())
+        return true;
+    std::vector<zsk_compress_desc_t> desc;
+    std::vector<void *> cds;
+    desc.swap(g.desc);
+    cds.swap(g.call_data);
+    const size_t in_used = g.in_used, out_used = g.out_used;
+    g.in_used = g.out_used = 0;
+    return gpu_batch(w, g.d_in, in_used, desc, out_used, &cds, nullptr, errbuf);
 }
 
 // Queue one frame for the GPU (the frame's bytes are copied: the caller may
@@ -320,6 +390,8 @@ static bool lz4_frame(zseek_writer *w, const void *src, size_t n, size_t content
     }
     w->frame_uc += n;
     w->frame_cm += c;
+    if (w->checksums)   // (GPU mode: a frame over 4 MiB, hashed where it is compressed)
+        w->frame_ck = (uint32_t)xxh64(src, n);
     return emit(w, w->cbuf.data(), c, call_data, errbuf) && log_frame(w, errbuf);
 }
 
@@ -335,6 +407,8 @@ static bool zstd_frame(zseek_writer *w, const void *src, size_t n, void *call_da
     }
     w->frame_uc += n;
     w->frame_cm += c;
+    if (w->checksums)
+        w->frame_ck = (uint32_t)xxh64(src, n);
     return emit(w, w->cbuf.data(), c, call_data, errbuf) && log_frame(w, errbuf);
 }
 
@@ -371,7 +445,23 @@ static bool end_frame(zseek_writer *w, void *call_data, char *errbuf)
         if (!emit(w, w->cbuf.data(), out.pos, call_data, errbuf))
             return false;
     } while (rem > 0);
+    if (w->checksums)   // the streamed frame's bytes, hashed as they were written (write_mt)
+        w->frame_ck = (uint32_t)w->hash.digest();
     return log_frame(w, errbuf);
+}
+
+extern "C" ZSEEK_EXPORT bool zsk_writer_set_checksums(zseek_writer_t *w, bool on)
+{
+    if (!w)
+        return false;
+    if (w->checksums == on)
+        return true;
+    // every frame of the table needs one: only before the first byte
+    if (!w->log.empty() || !w->gpu.desc.empty() || w->frame_uc || w->frame_cm || !w->ubuf.empty())
+        return false;
+    w->checksums = on;
+    w->hash.init();
+    return true;
 }
 
 extern "C" ZSEEK_EXPORT bool zsk_writer_set_gpu_compress(zseek_writer_t *w, size_t batch_bytes)
@@ -426,6 +516,9 @@ extern "C" ZSEEK_EXPORT zseek_writer_t *zseek_writer_open_full(zseek_write_file_
     w->type = type;
     w->min_frame_size = min_frame_size;
     memset(&w->prefs, 0, sizeof(w->prefs));
+    w->hash.init();
+    if (const char *e = getenv("ZSEEK_WRITE_CHECKSUMS"))
+        w->checksums = strtoull(e, nullptr, 10) != 0;
     if (type == ZSEEK_LZ4) {
         // ref compress.c:203-207
         w->prefs.compressionLevel = zsp ? zsp->params.lz4_params.compression_level : 0;
@@ -459,11 +552,17 @@ extern "C" ZSEEK_EXPORT zseek_writer_t *zseek_writer_open_full(zseek_write_file_
     }
     if (zsp && zsp->params.zstd_params.nb_workers > 1) {
         r = ZSTD_CCtx_setParameter(w->cctx, ZSTD_c_nbWorkers, zsp->params.zstd_params.nb_workers);
-        if (ZSTD_isError(r)) {
+        // A libzstd built without multithreading (Debian's 1.4.8, the one
+        // this library links) refuses any nbWorkers but 0.  nb_workers asks
+        // for speed, not for a format: the writer then streams the same
+        // frames (write_mt / end_frame) on the calling thread instead of
+        // refusing to open.  The reference fails here (compress.c:99-102).
+        const bool threads = !(ZSTD_isError(r) && ZSTD_getErrorCode(r) == ZSTD_error_parameter_unsupported);
+        if (threads && ZSTD_isError(r)) {
             set_error(errbuf, "%s: %s", "set nb of workers", ZSTD_getErrorName(r));
             goto fail;
         }
-        if (zsp->params.zstd_params.cpuset) {
+        if (threads && zsp->params.zstd_params.cpuset) {
             // create the worker pool while pinned to the caller's cpuset
             // (ref compress.c:105-139)
             pthread_t self = pthread_self();
@@ -526,6 +625,8 @@ static bool write_mt(zseek_writer *w, const void *buf, size_t len, void *call_da
             return false;
     } while (in.pos < in.size);
     w->frame_uc += len;
+    if (w->checksums)
+        w->hash.update(buf, len);
     return true;
 }
 
@@ -553,9 +654,125 @@ extern "C" ZSEEK_EXPORT bool zseek_write(zseek_writer_t *w, const void *buf, siz
     return true;
 }
 
-static size_t seek_table_size(size_t frames)
+// zseek_write over host copies of d_buf's pieces, through the pinned bounce
+// (zsk_write_device's host path; the device is current).
+static bool write_device_host(zseek_writer *w, const uint8_t *d_buf, size_t len, size_t piece, void *call_data,
+                              char *errbuf)
 {
-    return 8 + 8 * frames + 9;
+    const size_t need = std::max<size_t>(std::min(piece, len), 1);
+    if (w->bounce_cap < need) {
+        if (w->bounce)
+            (void)hipHostFree(w->bounce);
+        w->bounce = nullptr;
+        w->bounce_cap = 0;
+        if (hipHostMalloc((void **)&w->bounce, need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error(errbuf, "write from device: staging allocation failed");
+            return false;
+        }
+        w->bounce_cap = need;
+    }
+    size_t o = 0;
+    do {
+        const size_t n = std::min(piece, len - o);
+        for (size_t at = 0; at < n; at += kBouncePiece)
+            if (hipMemcpy(w->bounce + at, d_buf + o + at, std::min(kBouncePiece, n - at), hipMemcpyDeviceToHost) !=
+                hipSuccess) {
+                (void)hipGetLastError();
+                set_error(errbuf, "write from device: download failed");
+                return false;
+            }
+        if (!zseek_write(w, w->bounce, n, call_data, errbuf))
+            return false;
+        o += n;
+    } while (o < len);
+    return true;
+}
+
+extern "C" ZSEEK_EXPORT bool zsk_write_device(zseek_writer_t *w, const void *d_buf, size_t len, size_t write_size,
+                                              void *call_data, char *errbuf)
+{
+    if (!w) {
+        set_error(errbuf, "invalid writer");
+        return false;
+    }
+    GpuLz4 &g = w->gpu;
+    DeviceGuard keep;
+    int dev = g.device;
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if ((g.batch_bytes ? hipSetDevice(dev) : hipGetDevice(&dev)) != hipSuccess ||
+        ((len || d_buf) && (hipPointerGetAttributes(&attr, d_buf) != hipSuccess ||
+                            attr.type != hipMemoryTypeDevice || attr.device != dev))) {
+        (void)hipGetLastError();
+        set_error(errbuf, "write from device: not device memory of the writer's device");
+        return false;
+    }
+    const uint8_t *src = static_cast<const uint8_t *>(d_buf);
+    const size_t piece = write_size ? write_size : len;
+    const bool fast = g.batch_bytes && w->ubuf.empty() && len && piece >= w->min_frame_size && piece <= kGpuMaxFrame;
+    if (!fast) {
+        // zstd, GPU mode off, pieces the GPU path does not take or would
+        // buffer, bytes already buffered: the host path, piece by piece
+        return write_device_host(w, src, len, piece, call_data, errbuf) && gpu_flush(w, errbuf);
+    }
+    // Every whole piece is a direct frame without a content size (zseek_write
+    // with nothing buffered and len >= min_frame_size), and so is a last
+    // shorter piece of at least min_frame_size; compressed where they are.
+    if (!gpu_flush(w, errbuf))
+        return false;
+    const size_t tail = len % piece;
+    const size_t direct = tail >= w->min_frame_size ? len : len - tail;
+    const size_t limit = piece > 65536 ? g.batch_bytes : std::min(g.batch_bytes, kGpuDeviceBatch);
+    std::vector<zsk_compress_desc_t> desc;
+    for (size_t o = 0; o < direct;) {
+        desc.clear();
+        size_t in_bytes = 0, out_used = 0;
+        while (o < direct && desc.size() < g.max_frames) {
+            const size_t n = std::min(piece, direct - o);
+            if (!desc.empty() && in_bytes + n > limit)
+                break;
+            zsk_compress_desc_t d;
+            d.src_off = o;
+            d.dst_off = out_used;
+            d.src_size = (uint32_t)n;
+            d.flags = 0;
+            desc.push_back(d);
+            in_bytes += n;
+            out_used += ZSK_LZ4_COMPRESS_BOUND(n);
+            o += n;
+        }
+        if (!g.reserve_out(out_used)) {
+            (void)hipGetLastError();
+            g.failed = true;
+            set_error(errbuf, "%s: %s", "compress frame", "GPU staging allocation failed");
+            return false;
+        }
+        if (!gpu_batch(w, src, 0, desc, out_used, nullptr, call_data, errbuf))
+            return false;
+    }
+    if (direct < len) {   // a last piece under min_frame_size is buffered, as zseek_write buffers it
+        w->ubuf.resize(tail);
+        if (hipMemcpy(w->ubuf.data(), src + direct, tail, hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            w->ubuf.clear();
+            set_error(errbuf, "write from device: download failed");
+            return false;
+        }
+        w->frame_uc += tail;
+    }
+    return true;
+}
+
+// 8-byte entries, 12 with checksums (ref seek_table.c:374-407)
+static size_t seek_entry_size(const zseek_writer *w)
+{
+    return w->checksums ? 12 : 8;
+}
+
+static size_t seek_table_size(const zseek_writer *w, size_t frames)
+{
+    return 8 + seek_entry_size(w) * frames + 9;
 }
 
 extern "C" ZSEEK_EXPORT bool zseek_writer_close(zseek_writer_t *w, void *call_data, char *errbuf)
@@ -572,9 +789,12 @@ extern "C" ZSEEK_EXPORT bool zseek_writer_close(zseek_writer_t *w, void *call_da
         ok = false;
     }
     w->gpu.release();
+    if (w->bounce)
+        (void)hipHostFree(w->bounce);
     // seekable-format seek table (ref seek_table.c:365-419): skippable
-    // header, n x {cSize, dSize}, n, descriptor 0 (no checksums), magic
-    std::vector<uint8_t> t(seek_table_size(w->log.size()));
+    // header, n x {cSize, dSize[, checksum]}, n, descriptor (bit 7:
+    // checksums), magic
+    std::vector<uint8_t> t(seek_table_size(w, w->log.size()));
     auto put32 = [&](size_t at, uint32_t v) {
         t[at] = (uint8_t)v;
         t[at + 1] = (uint8_t)(v >> 8);
@@ -587,10 +807,12 @@ extern "C" ZSEEK_EXPORT bool zseek_writer_close(zseek_writer_t *w, void *call_da
     for (const FrameLogEntry &e : w->log) {
         put32(at, e.c_size);
         put32(at + 4, e.d_size);
-        at += 8;
+        if (w->checksums)
+            put32(at + 8, e.checksum);
+        at += seek_entry_size(w);
     }
     put32(at, (uint32_t)w->log.size());
-    t[at + 4] = 0;
+    t[at + 4] = w->checksums ? 0x80 : 0;
     put32(at + 5, 0x8F92EAB1u);
     if (!w->user_file.write(t.data(), t.size(), w->user_file.user_data, call_data) && ok) {
         set_error(errbuf, "write to file failed");
@@ -617,7 +839,7 @@ extern "C" ZSEEK_EXPORT bool zseek_writer_stats(zseek_writer_t *w, zseek_writer_
         return false;
     // ref compress.c:835-881
     size_t frames = w->log.size() + (w->frame_uc > 0 ? 1 : 0);
-    stats->seek_table_size = seek_table_size(w->log.size()) + (w->frame_uc > 0 ? 8 : 0);
+    stats->seek_table_size = seek_table_size(w, w->log.size()) + (w->frame_uc > 0 ? seek_entry_size(w) : 0);
     stats->seek_table_memory = sizeof(w->log) + w->log.capacity() * sizeof(FrameLogEntry);
     stats->frames = frames;
     stats->compressed_size = w->total_cm + w->frame_cm + stats->seek_table_size;

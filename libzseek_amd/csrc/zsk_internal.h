@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "../../include/zseek_hip.h"
+
 namespace zsk {
 
 // One seek-table frame of a batch (layout shared with zsk_frame_desc_t in
@@ -465,6 +467,15 @@ int launch_range_gather(const GatherSeg *d_seg, const uint64_t *d_cum, uint32_t 
 // ST_SEEK_CHECKSUM.
 int launch_frame_checksums(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_out,
                            const uint32_t *d_want, int32_t *d_status, hipStream_t stream);
+// ... and computed instead of compared (the same XXH64 body): d_sums[f] = the
+// low 32 bits of XXH64 of d_data[d_off, d_off + d_size) for every frame
+// (zsk_frame_checksums), or of d_src[src_off, src_off + src_size) for the
+// compressor's descriptors (the writer, next to launch_lz4_compress on the
+// same stream; the descriptors are read in place).  Asynchronous; 0 or -1.
+int launch_frame_checksums_compute(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_data,
+                                   uint32_t *d_sums, hipStream_t stream);
+int launch_src_checksums(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src,
+                         uint32_t *d_sums, hipStream_t stream);
 
 }   // namespace zsk
 

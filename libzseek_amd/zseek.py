@@ -111,6 +111,7 @@ EXPORTED = [
     "zsk_reader_set_devices", "zsk_reader_devices", "zsk_reader_set_io_threads",
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
     "zsk_preadv", "zsk_preadv_device", "zsk_gather_segments",
+    "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
 ]
 
 _lib = None
@@ -202,6 +203,12 @@ def lib() -> C.CDLL:
     L.zsk_gather_segments.restype = C.c_int
     L.zsk_gather_segments.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
+    L.zsk_frame_checksums.restype = C.c_int
+    L.zsk_frame_checksums.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.zsk_writer_set_checksums.restype = C.c_bool
+    L.zsk_writer_set_checksums.argtypes = [C.c_void_p, C.c_bool]
+    L.zsk_write_device.restype = C.c_bool
+    L.zsk_write_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_char_p]
     _lib = L
     return L
 
@@ -368,6 +375,19 @@ class Writer:
         """zsk_writer_set_gpu_compress: LZ4 frames of <= 4 MiB compressed on
         the GPU in batches (0 = 1 GiB, -1 = off)."""
         return bool(lib().zsk_writer_set_gpu_compress(self._h, batch_bytes & ((1 << 64) - 1)))
+
+    def set_checksums(self, on: bool = True) -> bool:
+        """zsk_writer_set_checksums: per-frame XXH64-low-32 checksums in the
+        seek table (only before anything has been written)."""
+        return bool(lib().zsk_writer_set_checksums(self._h, bool(on)))
+
+    def write_device(self, dev_ptr: int, length: int, write_size: int = 0,
+                     call_data: int | None = None) -> None:
+        """zsk_write_device: device memory [dev_ptr, dev_ptr + length) written
+        as zseek_write calls of write_size bytes would write it (0: one
+        write).  The bytes must be complete (synchronize their producer)."""
+        if not lib().zsk_write_device(self._h, dev_ptr, length, write_size, call_data, self._err):
+            raise ZseekError(self._err.value.decode())
 
     def stats(self) -> dict:
         s = WriterStatsC()
@@ -673,6 +693,23 @@ def verify_frame_checksums(desc, out, checksums, status, stream: int | None = No
     if lib().zsk_verify_frame_checksums(desc.data_ptr(), n, out.data_ptr(), checksums.data_ptr(),
                                         status.data_ptr(), stream) != 0:
         raise ZseekError("zsk_verify_frame_checksums launch failed")
+
+
+def frame_checksums(desc, data, out, stream: int | None = None) -> None:
+    """zsk_frame_checksums on torch device tensors (async): out[f] (int32 /
+    uint32, one per frame) = low 32 bits of XXH64 of data[d_off, d_off +
+    d_size) for each of desc's 24-byte zsk_frame_desc_t."""
+    import torch
+    n = out.numel()
+    if desc.numel() != n * 24:
+        raise ValueError("desc must hold 24 bytes per frame")
+    for t in (desc, data, out):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("frame_checksums needs contiguous device tensors")
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if lib().zsk_frame_checksums(desc.data_ptr(), n, data.data_ptr(), out.data_ptr(), stream) != 0:
+        raise ZseekError("zsk_frame_checksums launch failed")
 
 
 def gather_segments(seg, src, dst, status=None, stream: int | None = None) -> None:
