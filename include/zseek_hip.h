@@ -433,6 +433,97 @@ ZSEEK_EXPORT bool zsk_writer_set_checksums(zseek_writer_t *writer, bool on);
 ZSEEK_EXPORT bool zsk_write_device(zseek_writer_t *writer, const void *d_buf, size_t len,
     size_t write_size, void *call_data, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
+/*
+ * A reader over a complete seekable file (LZ4 or zstd frames plus seek
+ * table) that is already in device memory: @d_image[0, size), any alignment.
+ * The reader does not own the image; it must stay valid and unmodified until
+ * zseek_reader_close.  The reader's device is the one the pointer belongs to.
+ *
+ * Open downloads the file's tail, parses it with the same code as
+ * zseek_reader_open_full (a bad file gives the same NULL and errbuf text as
+ * a host copy of the bytes) and uploads the seek table once (prefix sums and,
+ * when the file carries them, checksums; counted in
+ * zsk_gpu_stats_t.device_memory).  NULL + errbuf also for no HIP device ("no
+ * HIP device available") and a pointer that is not device memory ("open
+ * device image: not device memory").
+ *
+ * Every read call (zseek_pread, zseek_read, zsk_pread_device, zsk_preadv,
+ * zsk_preadv_device) behaves as on a reader opened over a host copy of the
+ * image -- return values, bytes, errbuf, cache, partial-read rules,
+ * zsk_reader_set_verify_checksums -- but no compressed byte is staged or
+ * uploaded: the decode kernels read the frames in place, and
+ * zsk_gpu_stats_t.bytes_uploaded stays 0.  A contiguous read's descriptors
+ * are written on the device from the resident table; a vectored batch uploads
+ * only its descriptors, segments and their prefix sum.  zstd reads of <= 64
+ * frames plan on the device (one stream synchronization more than on a host
+ * image).  A vectored batch is also cut where the compressed distance between
+ * its first and last touched frame would pass 4 x zsk_reader_set_batch_bytes
+ * (256 MiB by default): the LZ4 parse scratch of a batch decoded in place
+ * grows with that distance, and the parse kernels address a wave's frames
+ * through one 32-bit buffer resource (with batch_bytes of 512 MiB or more a
+ * batch spanning 2 GiB fails the call: "vectored read: a batch spans 2 GiB of
+ * the device image").
+ *
+ * What must be readable around the image: the kernels load whole aligned
+ * words, so they may read the bytes between the 32-byte boundary below
+ * @d_image and @d_image, and up to the 4-byte boundary past a frame's end --
+ * for the last frame that lies inside the seek table (>= 17 bytes) that
+ * follows it.  Nothing at or past @d_image + size is read by a kernel: any
+ * allocation's own rounding covers the low end, the file itself the high.
+ * Open only sums the seek table's entries, so a corrupt table can put frames
+ * past the end of the file: a read whose compressed span is not inside
+ * [0, size) fails with "unexpected EOF" before any kernel runs, where the
+ * pread callback of a host copy comes back short (a span that ends exactly at
+ * @size may be read up to the 4-byte boundary after it).
+ *
+ * One lane: zsk_reader_set_devices returns true only for exactly that one
+ * device (and changes nothing), zsk_reader_devices reports it from open on,
+ * zsk_reader_set_io_threads is accepted and has no effect.
+ */
+ZSEEK_EXPORT zseek_reader_t *zsk_reader_open_device(const void *d_image, size_t size,
+    size_t cache_size, char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * A complete seekable LZ4 file built in device memory.  The call leaves in
+ * @d_image[0, returned size) the bytes this sequence writes: a writer opened
+ * with {ZSEEK_LZ4, @level} and min_frame_size = @frame_size,
+ * zsk_writer_set_checksums(@flags & ZSK_IMAGE_CHECKSUMS),
+ * zsk_write_device(w, d_src, len, frame_size, ...), zseek_writer_close --
+ * direct frames of @frame_size bytes, a shorter last piece as the buffered
+ * frame with its content-size header, then the seek table (8-byte entries, 12
+ * with checksums); len == 0 gives the empty table alone.  No frame byte, slot
+ * or per-frame size crosses to the host: frames are compressed from @d_src in
+ * batches of at most @batch_bytes input bytes (0: 256 MiB, 1 GiB for frames
+ * above 64 KiB, as zsk_write_device; at least one frame) into pooled slots,
+ * packed into the image by zsk_gather_segments' kernel at offsets scanned on
+ * the device, and the table is written there too.  Synchronous (one host
+ * synchronization, at the end); @d_src and @d_image (any alignment) are
+ * memory of one device and must not overlap.  The bytes of @d_src must be
+ * complete when the call is made (their producer synchronized), as for
+ * zsk_write_device.  The scratch (a batch's slots at their bound, 64 KiB of
+ * compressor tables per batch frame, 12 bytes per frame of the file) is
+ * sized by the largest call so far and stays allocated for the life of the
+ * process, one set per device (up to four under concurrent calls): about
+ * 0.5 GiB after a default call on 64 KiB frames, 1.1 GiB on frames above;
+ * pass a smaller @batch_bytes to hold less.
+ *
+ * zsk_lz4_image_bound(len, frame_size, flags): the capacity the call asks
+ * for -- every frame at its ZSK_LZ4_COMPRESS_BOUND, plus the table
+ * (17 + 8 or 12 bytes per frame); 0 for frame_size == 0.
+ *
+ * Returns the file's size, or -1 + errbuf for frame_size == 0 or above
+ * ZSK_LZ4_COMPRESS_MAX_FRAME, level >= 3, more frames than a seek table
+ * holds, pointers that are not device memory of one device, @capacity below
+ * the bound ("build image: buffer too small", checked before anything is
+ * written) and a HIP failure.  Nothing at or past @d_image + @capacity is ever
+ * written; bytes between the returned size and @capacity are unspecified.
+ */
+#define ZSK_IMAGE_CHECKSUMS 1u
+ZSEEK_EXPORT size_t zsk_lz4_image_bound(size_t len, size_t frame_size, unsigned flags);
+ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t frame_size,
+    int level, unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,5 +10,5 @@ from .zseek import (  # noqa: F401
     seek_table_of, status_string, lz4_compress_bound, lz4_compress_frames, lz4_compress_layout,
     lz4_compress_scratch_size, gather_segments, frame_checksums, RANGE_DTYPE, SEGMENT_DTYPE,
     synth_buffer, tools, verify_frame_checksums, with_frame_checksums, zstd_decode_frames,
-    zstd_seekable, zstd_tool_version,
+    zstd_seekable, zstd_tool_version, lz4_image_bound, lz4_build_image,
 )

@@ -39,6 +39,7 @@
 
 #include <algorithm>
 
+#include "block_scan.h"
 #include "pool.h"
 #include "zsk_internal.h"
 
@@ -61,20 +62,12 @@ __global__ __launch_bounds__(kScanT) void range_scan_kernel(const GatherSeg *__r
 {
     __shared__ uint64_t s_sum[kScanT];
     const uint32_t t = threadIdx.x;
-    const uint32_t per = (nseg + kScanT - 1) / kScanT;
-    const uint32_t a = std::min<uint64_t>((uint64_t)per * t, nseg), b = std::min<uint64_t>((uint64_t)per * (t + 1), nseg);
+    uint32_t a, b;
+    block_share<kScanT>(nseg, t, &a, &b);
     uint64_t sum = 0;
     for (uint32_t i = a; i < b; i++)
         sum += seg[i].len;
-    s_sum[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < kScanT; d <<= 1) {   // inclusive scan of the shares
-        const uint64_t y = t >= d ? s_sum[t - d] : 0;
-        __syncthreads();
-        s_sum[t] += y;
-        __syncthreads();
-    }
-    uint64_t run = s_sum[t] - sum;
+    uint64_t run = block_scan_inclusive<kScanT>(s_sum, t, sum) - sum;   // (block_scan.h)
     if (t == 0)
         cum[0] = 0;
     for (uint32_t i = a; i < b; i++) {

@@ -70,8 +70,12 @@ inline uint64_t range_end(const RangeReq &q, uint64_t size)
     return q.count < size - q.offset ? q.offset + q.count : size;   // (offset < size)
 }
 
+// c_off / span_limit (optional; a reader over a device image, whose frames are
+// decoded where they lie instead of packed): a batch also ends where the
+// compressed distance from its first frame's start to a frame's end would
+// exceed span_limit (a frame longer than that is a batch of its own).
 inline RangePlan plan_ranges(const RangeReq *rg, size_t n, const uint64_t *d_off, size_t nframes,
-                             uint64_t batch_bytes)
+                             uint64_t batch_bytes, const uint64_t *c_off = nullptr, uint64_t span_limit = 0)
 {
     RangePlan P;
     P.rt0.assign(n, 0);
@@ -117,6 +121,8 @@ inline RangePlan plan_ranges(const RangeReq *rg, size_t n, const uint64_t *d_off
         while (t < T) {
             const uint64_t d = d_off[P.frames[t] + 1] - d_off[P.frames[t]];
             if (t > b.t0 && b.d_bytes + d > batch_bytes)
+                break;
+            if (t > b.t0 && c_off && c_off[P.frames[t] + 1] - c_off[P.frames[b.t0]] > span_limit)
                 break;
             if (t == b.t0 || P.frames[t] != P.frames[t - 1] + 1)
                 P.runs.push_back({P.frames[t], P.frames[t] + 1});

@@ -68,8 +68,28 @@ constexpr size_t kFirstBatch = 4u << 20;       // the first batch of a request (
 constexpr size_t kLaneMin = 1u << 20;          // decoded bytes per lane, at least
 }   // namespace
 
+// A seekable file in device memory (zsk_reader_open_device): the frames are
+// decoded where they are.  The decode kernels get `base`, the image's start
+// rounded down to 256 bytes (the alignment of the hipMalloc'd staging they
+// otherwise read: zstd_decode.hip aligns its spans by c_off alone, so the base
+// itself must be 16-byte aligned), and descriptors whose c_off carry `bias`.
+struct DeviceImage {
+    const uint8_t *ptr = nullptr;    // the caller's image (not owned)
+    size_t size = 0;
+    int device = -1;
+    const uint8_t *base = nullptr;   // ptr rounded down to 256
+    uint64_t bias = 0;               // ptr - base
+    // the seek table, uploaded at open: c_off[n + 1], d_off[n + 1], then the
+    // n checksums when the file carries them
+    uint64_t *d_table = nullptr;
+    size_t table_bytes = 0;
+    const uint64_t *d_coff = nullptr, *d_doff = nullptr;
+    const uint32_t *d_ck = nullptr;
+};
+
 struct zseek_reader {
     zseek_read_file_t user_file;
+    DeviceImage *img = nullptr;   // NULL: the file comes through user_file
     zseek_compression_type_t type;
     // the reference's rwlock (decompress.c:38): shared for cache hits
     // (:699-706), exclusive for misses, no-cache reads and GPU batches
@@ -192,6 +212,96 @@ extern "C" ZSEEK_EXPORT zseek_reader_t *zseek_reader_open(FILE *cfile, size_t ca
     return zseek_reader_open_full(uf, cache_size, call_data, errbuf);
 }
 
+// ---------------------------------------------------------------------------
+// zsk_reader_open_device: the file is in device memory.  Open reads it through
+// these two callbacks (a few small downloads: the magic, the footer, the
+// table), so the parse and its error texts are zseek_reader_open_full's; no
+// read ever calls them again (submit / submit_gather never enter read_span).
+// ---------------------------------------------------------------------------
+static ssize_t image_pread(void *data, size_t size, size_t offset, void *user_data, void *call_data)
+{
+    (void)call_data;
+    const DeviceImage *img = static_cast<const DeviceImage *>(user_data);
+    if (offset >= img->size)
+        return 0;
+    const size_t n = std::min(size, img->size - offset);
+    if (n && hipMemcpy(data, img->ptr + offset, n, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return (ssize_t)n;
+}
+
+static ssize_t image_fsize(void *user_data, void *call_data)
+{
+    (void)call_data;
+    return (ssize_t)static_cast<const DeviceImage *>(user_data)->size;
+}
+
+extern "C" ZSEEK_EXPORT zseek_reader_t *zsk_reader_open_device(const void *d_image, size_t size, size_t cache_size,
+                                                               char *errbuf)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        (void)hipGetLastError();
+        set_error(errbuf, "no HIP device available");
+        return nullptr;
+    }
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if (!d_image || hipPointerGetAttributes(&attr, d_image) != hipSuccess || attr.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        set_error(errbuf, "open device image: not device memory");
+        return nullptr;
+    }
+    DeviceImage *img = new (std::nothrow) DeviceImage();
+    if (!img) {
+        set_error_errno(errbuf, "allocate reader", ENOMEM);
+        return nullptr;
+    }
+    img->ptr = static_cast<const uint8_t *>(d_image);
+    img->size = size;
+    img->device = attr.device;
+    img->bias = reinterpret_cast<uintptr_t>(d_image) & 255;
+    img->base = img->ptr - img->bias;
+    DeviceGuard keep;
+    if (hipSetDevice(img->device) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(errbuf, "invalid HIP device %d", img->device);
+        delete img;
+        return nullptr;
+    }
+    const zseek_read_file_t uf = {img, image_pread, image_fsize};
+    zseek_reader *r = zseek_reader_open_full(uf, cache_size, nullptr, errbuf);
+    if (!r) {
+        delete img;
+        return nullptr;
+    }
+    r->img = img;
+    r->devices.assign(1, img->device);
+    // the table, once: a batch's descriptors and checksum words come from it
+    const size_t n = r->st.frames();
+    const size_t sums = r->st.checksum_flag ? n * sizeof(uint32_t) : 0;
+    img->table_bytes = 2 * (n + 1) * sizeof(uint64_t) + sums;
+    bool ok = !r->st.c_off.empty() && hipMalloc((void **)&img->d_table, img->table_bytes) == hipSuccess;
+    if (ok) {
+        uint64_t *const c = img->d_table, *const d = c + n + 1;
+        ok = hipMemcpy(c, r->st.c_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(d, r->st.d_off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
+             (!sums || hipMemcpy(d + n + 1, r->st.checksum.data(), sums, hipMemcpyHostToDevice) == hipSuccess);
+        img->d_coff = c;
+        img->d_doff = d;
+        img->d_ck = sums ? reinterpret_cast<const uint32_t *>(d + n + 1) : nullptr;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        set_error(errbuf, "open device image: seek table upload failed");
+        zseek_reader_close(r, nullptr, nullptr);
+        return nullptr;
+    }
+    return r;
+}
+
 extern "C" ZSEEK_EXPORT bool zseek_reader_close(zseek_reader_t *reader, void *call_data,
                                                 char *errbuf)
 {
@@ -199,6 +309,13 @@ extern "C" ZSEEK_EXPORT bool zseek_reader_close(zseek_reader_t *reader, void *ca
     (void)errbuf;
     if (!reader)
         return true;   // ref decompress.c:362-363
+    if (DeviceImage *img = reader->img) {
+        // (every read is synchronous: nothing of the lanes still reads the table)
+        DeviceGuard keep;
+        if (img->d_table && hipSetDevice(img->device) == hipSuccess)
+            (void)hipFree(img->d_table);
+        delete img;
+    }
     delete reader->cache;
     delete reader;     // lanes: streams drained, scratch and buffers freed
     return true;
@@ -396,6 +513,19 @@ bool read_span(LaneJob &J, uint8_t *dst, uint64_t len, uint64_t off)
     return true;
 }
 
+// read_span's stand-in for a file in device memory, whose frames are decoded
+// where they are: nothing is read, but a compressed span that the seek table
+// puts past the end of the image (a corrupt or hostile table: open only sums
+// its entries) fails exactly where the pread of a host copy comes back short,
+// before any kernel gets a descriptor that points outside the image.
+bool image_span(LaneJob &J, const DeviceImage *img, uint64_t len, uint64_t off)
+{
+    if (off <= img->size && len <= img->size - off)
+        return true;
+    set_error(J.err, "unexpected EOF");
+    return false;
+}
+
 #ifdef ZSK_TUNING
 // tuning builds, ZSEEK_HOST_TIMERS: a batch's host steps (ns, summed):
 // [0] submit to after the read, [1] read to queued, [2] finish's wait, [3]
@@ -460,17 +590,23 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     // waits for them anyway
     if (br.h_len > s.h_out_cap)
         pool_wait(&s.copies);
+    // a file in device memory: the frames are decoded where they are -- no
+    // read, no staging, no upload; d_comp holds the descriptors alone, written
+    // by image_desc_kernel from the resident table
+    const DeviceImage *const img = r->img;
     // the descriptors ride behind the compressed span (past its 256-byte
     // read slack) in the same pinned buffer and the same upload
-    const uint64_t doff = (csz + 256 + 255) & ~255ull;
-    // (zstd, a request's few frames: the host plan rides behind them too)
-    const bool zplan = r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
+    const uint64_t doff = img ? 0 : (csz + 256 + 255) & ~255ull;
+    // (zstd, a request's few frames: the host plan rides behind them too;
+    // not for a device image, whose bytes the host never sees: the device
+    // plan and its synchronization)
+    const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
     const uint64_t poff = doff + n * sizeof(FrameDesc), up = poff + (zplan ? 16 * (n + 1) : 0);
     if (!s.reserve(up, dsz, br.h_len, n, ck, J.err)) {
         J.io_failed = true;
         return false;
     }
-    if (csz && !read_span(J, s.h_comp, csz, c0)) {
+    if (csz && !(img ? image_span(J, img, csz, c0) : read_span(J, s.h_comp, csz, c0))) {
         J.io_failed = true;
         return false;
     }
@@ -478,10 +614,15 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     HT_T(ht1)
     FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + doff);
     const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + doff);
+    // what the kernels read the frames from: the slot's staging, or the image
+    // in place (its 256-aligned base; the descriptors' c_off carry the rest)
+    const uint8_t *const comp = img ? img->base : s.d_comp;
+    const uint64_t c_rel = img ? img->bias : 0 - c0;
     uint32_t max_dsize = 0;
+    // (a device image: the host copy only sizes the split decoder's scratch)
     for (size_t i = 0; i < n; i++) {
         FrameDesc &d = h_desc[i];
-        d.c_off = st.c_off[f0 + i] - c0;
+        d.c_off = st.c_off[f0 + i] + c_rel;
         d.d_off = st.d_off[f0 + i] - d0;
         d.c_size = (uint32_t)st.csize(f0 + i);
         d.d_size = (uint32_t)st.dsize(f0 + i);
@@ -511,7 +652,11 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     // (the LZ4 two-phase decoder's plan kernel initializes both itself, the
     // zstd sequence kernel writes both for every frame)
     const bool lz4_split = r->type == ZSEEK_LZ4 && lz4_pick_engine((uint32_t)n) != ENGINE_WAVE;
-    if (host_dma)
+    if (img) {
+        if (launch_image_desc(img->d_coff, img->d_doff, f0, (uint32_t)n, img->bias,
+                              reinterpret_cast<FrameDesc *>(s.d_comp), s.stream) != 0)
+            e = hipErrorLaunchFailure;
+    } else if (host_dma)
         e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, s.stream);
     else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, s.stream) != 0)
         e = hipErrorLaunchFailure;
@@ -526,12 +671,12 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
         (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
                                             (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
                                             stop_last)
-                            : zstd_decode_frames(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs,
+                            : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs,
                                                  s.stream, d_fail, stop_last)) != 0)
         e = hipErrorLaunchFailure;
     if (e == hipSuccess && r->type == ZSEEK_LZ4) {
         if (lz4_pick_engine((uint32_t)n) == ENGINE_WAVE) {
-            if (launch_lz4_wave(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
+            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
                 e = hipErrorLaunchFailure;
         } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
                                          s.stream) != 0) {
@@ -558,7 +703,7 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
                 post.seq = s.seq;
             }
             bool posted = false;
-            if (launch_lz4_split(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
+            if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
                                  ROUTE_AUTO, 15, 0, stop_last, max_dsize, want_post ? &post : nullptr,
                                  &posted, true) != 0)
                 e = hipErrorLaunchFailure;
@@ -568,10 +713,14 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     // seek-table checksums (descriptor bit 7) when asked for: XXH64 low 32
     // bits of every decoded frame, on the GPU (frame_check.hip)
     if (e == hipSuccess && ck) {
-        memcpy(s.h_ck, st.checksum.data() + f0, n * sizeof(uint32_t));
-        e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
+        // (a device image: the batch's n words of the resident table, at f0)
+        const uint32_t *d_want = img ? img->d_ck + f0 : s.d_ck;
+        if (!img) {
+            memcpy(s.h_ck, st.checksum.data() + f0, n * sizeof(uint32_t));
+            e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
+        }
         if (e == hipSuccess &&
-            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, s.d_ck, s.d_status, s.stream) != 0)
+            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, d_want, s.d_status, s.stream) != 0)
             e = hipErrorLaunchFailure;
     }
     // decoded bytes out: straight into a device destination (a peer copy from
@@ -624,7 +773,7 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     g.batches++;
     g.frames_decoded += n;
     g.bytes_decoded += dsz;
-    g.bytes_uploaded += csz;
+    g.bytes_uploaded += img ? 0 : csz;
     HT_ADD(1, ht1)
 #ifdef ZSK_TUNING
     t_queued = ht_now();
@@ -1019,10 +1168,16 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     (void)hipSetDevice(g.device);
     if (h_len > s.h_out_cap)
         pool_wait(&s.copies);
+    // a file in device memory: nothing is read or packed -- the touched frames
+    // are decoded where they are, from host-built descriptors (the host has
+    // the whole table, and a vectored batch's d_off is a scan over its sparse
+    // frame list; they ride in the small upload that carries the segments
+    // anyway, so a device-side builder would save no transfer)
+    const DeviceImage *const img = r->img;
     // behind the packed compressed bytes and their 256-byte read slack: the
     // descriptors, the zstd host plan, the segments, their prefix sum
-    const uint64_t doff = (csz + 256 + 255) & ~255ull;
-    const bool zplan = r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
+    const uint64_t doff = img ? 0 : (csz + 256 + 255) & ~255ull;
+    const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
     const uint64_t poff = doff + n * sizeof(FrameDesc), goff = poff + (zplan ? 16 * (n + 1) : 0);
     const uint64_t coff = goff + nseg * sizeof(GatherSeg), up = coff + (nseg + 1) * sizeof(uint64_t);
     if (!s.reserve(up, pack_at + h_len, h_len, n, ck, V.J.err)) {
@@ -1030,22 +1185,31 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
         return false;
     }
     uint64_t c_at = 0;
-    for (size_t ri = b.r0; ri < b.r1; ri++) {   // one pread per run of adjacent frames
+    for (size_t ri = b.r0; ri < b.r1; ri++) {   // one pread per run of adjacent frames (an image: its bounds)
         const uint64_t c0 = st.c_off[P.runs[ri].f0], len = st.c_off[P.runs[ri].f1] - c0;
-        if (len && !read_span(V.J, s.h_comp + c_at, len, c0)) {
+        if (len && !(img ? image_span(V.J, img, len, c0) : read_span(V.J, s.h_comp + c_at, len, c0))) {
             V.J.io_failed = true;
             return false;
         }
         c_at += len;
     }
+    // (the parse kernels address a wave's frames through one 32-bit buffer
+    // resource: the planner's span cut keeps a batch far below it unless
+    // batch_bytes was set to 512 MiB or more)
+    if (img && n && st.c_off[P.frames[b.t1 - 1] + 1] - st.c_off[P.frames[b.t0]] >= 0x7FFFFF00ull) {
+        set_error(V.J.err, "vectored read: a batch spans 2 GiB of the device image");
+        V.J.io_failed = true;
+        return false;
+    }
     FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + doff);
     const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + doff);
+    const uint8_t *const comp = img ? img->base : s.d_comp;
     uint32_t max_dsize = 0;
     uint64_t c = 0, d = 0;
     for (size_t i = 0; i < n; i++) {
         const size_t f = P.frames[b.t0 + i];
         FrameDesc &fd = h_desc[i];
-        fd.c_off = c;
+        fd.c_off = img ? st.c_off[f] + img->bias : c;
         fd.d_off = d;
         fd.c_size = (uint32_t)st.csize(f);
         fd.d_size = (uint32_t)st.dsize(f);
@@ -1084,17 +1248,17 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
         (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
                                             (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
                                             stop_last)
-               : zstd_decode_frames(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
+               : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
                                     stop_last)) != 0)
         e = hipErrorLaunchFailure;
     if (e == hipSuccess && r->type == ZSEEK_LZ4) {
         if (wave) {
-            if (launch_lz4_wave(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
+            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
                 e = hipErrorLaunchFailure;
         } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
                                          s.stream) != 0) {
             e = hipErrorOutOfMemory;
-        } else if (launch_lz4_split(d_desc, (uint32_t)n, s.d_comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
+        } else if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
                                     ROUTE_AUTO, 15, 0, stop_last, max_dsize, nullptr, nullptr, true) != 0) {
             e = hipErrorLaunchFailure;
         }
@@ -1138,7 +1302,7 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     g.batches++;
     g.frames_decoded += n;
     g.bytes_decoded += dsz;
-    g.bytes_uploaded += csz;
+    g.bytes_uploaded += img ? 0 : csz;
     return true;
 }
 
@@ -1213,7 +1377,13 @@ ssize_t preadv_frames(zseek_reader *r, void *buf, zsk_range_t *ranges, size_t nr
     const size_t nframes = st.frames();
     const uint64_t zero = 0;
     const uint64_t *const d_off = nframes ? st.d_off.data() : &zero;
-    const RangePlan P = plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
+    // a device image's frames are decoded where they lie: the LZ4 plan lays
+    // item slots out by compressed distance and the parse kernels address a
+    // wave's frames through one 32-bit resource, so a batch of sparse frames is
+    // also cut by the compressed span it covers (4 x batch_bytes: 256 MiB by default)
+    const RangePlan P = r->img && nframes ? plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes,
+                                                        st.c_off.data(), (uint64_t)std::min<size_t>(r->batch_bytes, SIZE_MAX / 4) * 4)
+                                          : plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
     VecJob V;
     V.P = &P;
     V.buf = static_cast<uint8_t *>(buf);
@@ -1483,7 +1653,8 @@ extern "C" ZSEEK_EXPORT bool zsk_reader_gpu_stats_ex(zseek_reader_t *reader, zsk
     memset(&s, 0, sizeof(s));
     {
         std::unique_lock<std::shared_mutex> guard(reader->lock);
-        s.device = reader->lanes.empty() ? -1 : reader->lanes[0]->device;
+        s.device = reader->img ? reader->img->device : reader->lanes.empty() ? -1 : reader->lanes[0]->device;
+        s.device_memory = reader->img ? reader->img->table_bytes : 0;   // the resident seek table
         s.copy_threads = copy_pool_threads();
         s.io_parts = io_parts(reader);
         for (auto &l : reader->lanes) {
@@ -1549,6 +1720,9 @@ extern "C" ZSEEK_EXPORT bool zsk_reader_set_devices(zseek_reader_t *reader, cons
     for (int i = 0; i < n; i++)
         if (devices[i] < 0 || devices[i] >= count)
             return false;
+    // a reader over a device image has one lane, on the image's device
+    if (reader->img)
+        return n == 1 && devices[0] == reader->img->device;
     std::unique_lock<std::shared_mutex> guard(reader->lock);
     reader->lanes.clear();   // drains and frees the old lanes
     reader->devices.assign(devices, devices + n);

@@ -477,6 +477,15 @@ int launch_frame_checksums_compute(const FrameDesc *d_desc, uint32_t nframes, co
 int launch_src_checksums(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src,
                          uint32_t *d_sums, hipStream_t stream);
 
+// A reader over a seekable file in device memory (image_build.hip,
+// image_desc_kernel): the descriptors of the n frames from f0 on, written on
+// the device from the reader's resident prefix sums (n_frames + 1 entries
+// each): c_off = d_coff[f] + c_bias (the image's start relative to the d_comp
+// base the decode kernels get), d_off = d_doff[f] - d_doff[f0].  Asynchronous
+// on stream; 0 or -1.
+int launch_image_desc(const uint64_t *d_coff, const uint64_t *d_doff, uint64_t f0, uint32_t n, uint64_t c_bias,
+                      FrameDesc *d_desc, hipStream_t stream);
+
 }   // namespace zsk
 
 #endif

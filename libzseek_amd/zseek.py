@@ -112,6 +112,7 @@ EXPORTED = [
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
     "zsk_preadv", "zsk_preadv_device", "zsk_gather_segments",
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
+    "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
 ]
 
 _lib = None
@@ -209,6 +210,13 @@ def lib() -> C.CDLL:
     L.zsk_writer_set_checksums.argtypes = [C.c_void_p, C.c_bool]
     L.zsk_write_device.restype = C.c_bool
     L.zsk_write_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_char_p]
+    L.zsk_reader_open_device.restype = C.c_void_p
+    L.zsk_reader_open_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_char_p]
+    L.zsk_lz4_image_bound.restype = C.c_size_t
+    L.zsk_lz4_image_bound.argtypes = [C.c_size_t, C.c_size_t, C.c_uint]
+    L.zsk_lz4_build_image.restype = C.c_ssize_t
+    L.zsk_lz4_build_image.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_uint, C.c_size_t,
+                                      C.c_void_p, C.c_size_t, C.c_char_p]
     _lib = L
     return L
 
@@ -434,6 +442,23 @@ class Reader:
                                                self._err)
         if not self._h:
             raise ZseekError(self._err.value.decode())
+
+    @classmethod
+    def open_device(cls, dev_ptr: int, size: int, cache_size: int = 0) -> "Reader":
+        """zsk_reader_open_device: a reader over a seekable file that is in
+        device memory at [dev_ptr, dev_ptr + size).  The caller keeps that
+        memory alive and unmodified until close(); no read stages or uploads
+        a compressed byte (gpu_stats()["bytes_uploaded"] stays 0)."""
+        self = cls.__new__(cls)
+        self.image = None
+        self.size = size
+        self.npreads = 0
+        self._cbs = ()
+        self._err = C.create_string_buffer(ERRBUF)
+        self._h = lib().zsk_reader_open_device(dev_ptr, size, cache_size, self._err)
+        if not self._h:
+            raise ZseekError(self._err.value.decode())
+        return self
 
     @property
     def error(self) -> str:
@@ -780,6 +805,38 @@ def lz4_compress_frames(desc, src, dst, csize, level: int = 0, scratch=None,
     if lib().zsk_lz4_compress_frames(desc.data_ptr(), n, src.data_ptr(), dst.data_ptr(),
                                      csize.data_ptr(), level, scratch.data_ptr(), stream) != 0:
         raise ZseekError("zsk_lz4_compress_frames launch failed")
+
+
+IMAGE_CHECKSUMS = 1   # ZSK_IMAGE_CHECKSUMS
+
+
+def lz4_image_bound(length: int, frame_size: int, checksums: bool = False) -> int:
+    """zsk_lz4_image_bound: the capacity zsk_lz4_build_image asks for."""
+    return int(lib().zsk_lz4_image_bound(length, frame_size, IMAGE_CHECKSUMS if checksums else 0))
+
+
+def lz4_build_image(src, frame_size: int, level: int = 0, checksums: bool = False, batch_bytes: int = 0,
+                    image=None):
+    """zsk_lz4_build_image: the uint8 device tensor `src` as a complete
+    seekable LZ4 file in device memory (synchronous).  `image`: the uint8
+    device tensor to build it in (default: a new one of lz4_image_bound
+    bytes).  -> the file, a view of `image`."""
+    import torch
+    if not src.is_cuda or not src.is_contiguous() or src.dtype != torch.uint8:
+        raise ValueError("lz4_build_image needs a contiguous uint8 device tensor")
+    if image is None:
+        image = torch.empty(max(lz4_image_bound(src.numel(), frame_size, checksums), 1), dtype=torch.uint8,
+                            device=src.device)
+    if not image.is_cuda or not image.is_contiguous() or image.dtype != torch.uint8:
+        raise ValueError("lz4_build_image needs a contiguous uint8 device tensor to build in")
+    torch.cuda.current_stream(src.device).synchronize()   # the bytes must be complete
+    err = C.create_string_buffer(ERRBUF)
+    n = lib().zsk_lz4_build_image(src.data_ptr() if src.numel() else None, src.numel(), frame_size, level,
+                                  IMAGE_CHECKSUMS if checksums else 0, batch_bytes, image.data_ptr(),
+                                  image.numel(), err)
+    if n < 0:
+        raise ZseekError(err.value.decode())
+    return image[:n]
 
 
 def with_frame_checksums(image, checksums) -> np.ndarray:
