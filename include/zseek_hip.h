@@ -22,6 +22,8 @@
  *                            read), as one call: the touched frames decoded
  *                            in one grid per batch; zsk_gather_segments is
  *                            its device-side segmented copy.
+ *   zsk_preadv_device_async — the same read queued on the caller's stream,
+ *                            its per-range results left in device memory.
  *   zsk_verify_frame_checksums — the seek table's per-frame checksum,
  *                            parsed by seek_table.c:95-97 and never checked
  *                            there, checked on the GPU.
@@ -219,6 +221,72 @@ ZSEEK_EXPORT ssize_t zsk_preadv(zseek_reader_t *reader, void *buf,
 ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf,
     zsk_range_t *ranges, size_t nranges, void *call_data,
     char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * zsk_preadv_device, stream-ordered: the same read queued on @stream (a
+ * hipStream_t of the reader's first lane's device; NULL: HIP's null stream).
+ * Everything the call does on the GPU is ordered after what @stream already
+ * holds and before what is queued on it afterwards; the call does not wait on
+ * the host for its own work and returns 0 once everything is queued, -1 +
+ * errbuf otherwise.  A consumer kernel queued on @stream behind the call sees
+ * the bytes and the results.
+ *
+ * @ranges is a host array, read during the call (it may be reused on return);
+ * its `result` fields are not written.  The results go to @d_result, device
+ * memory of nranges + 1 int64_t: when the stream reaches the end of the
+ * call's work, d_result[i] holds exactly what zsk_preadv_device would have put
+ * in ranges[i].result (the full count when every touched frame decoded, short
+ * at EOF, 0 for an empty range or one at / past EOF, the bytes before the
+ * first failed frame, -1 when the first frame fails) and d_result[nranges]
+ * what it would have returned: the number of ranges delivered in full.  The
+ * bytes in @d_buf follow zsk_preadv_device's rules: disjoint destinations,
+ * nothing outside a range's destination written, bytes past `result`
+ * unspecified.  No error text can be deferred: errbuf is written only for
+ * failures the call itself sees.  For the "decompress frame: ..." text of a
+ * failed range, repeat that range with zsk_preadv_device.
+ *
+ * Honours zsk_reader_set_verify_checksums and zsk_reader_set_batch_bytes like
+ * the synchronous call; neither consults nor fills the frame cache; holds the
+ * reader's exclusive lock for the duration of the call (the enqueue) only;
+ * the GPU counters (batches, frames_decoded, bytes_decoded, bytes_uploaded)
+ * advance at enqueue.
+ *
+ * LZ4 readers only, over a host image or a device image
+ * (zsk_reader_open_device).  A zstd reader: -1, "asynchronous read: zstd is
+ * not supported".  On a host image the pread callbacks run on the calling
+ * thread during the call, one per run of adjacent touched frames; only the
+ * GPU work is deferred.
+ *
+ * -1 and nothing queued for: a NULL reader ("invalid reader"); a stream that
+ * is capturing ("asynchronous read: stream is capturing" -- the call reuses
+ * pinned staging, so it must never end up in a graph); a zstd reader; NULL
+ * @ranges or NULL @d_result with nranges > 0; NULL @d_buf when some range has
+ * bytes ("invalid buffer"); no device.  nranges == 0 returns 0 and queues only
+ * d_result[0] = 0 (nothing for a NULL @d_result).  The call may also fail
+ * after some batches were queued -- a pread callback failure, "unexpected
+ * EOF", a batch spanning 2 GiB of a device image, a HIP error: it then still
+ * queues a fill of d_result[0 .. nranges] with -1, so a stream-ordered
+ * consumer sees the failure, and returns -1 + the usual text; @d_buf is then
+ * unspecified inside the ranges' destinations and untouched outside them.
+ *
+ * Host waits the call may make: (1) growing a batch slot's buffers, the LZ4
+ * parse scratch or the per-call table -- at first use and after a larger call
+ * (freeing device memory waits for the device); (2) reusing a batch slot or a
+ * per-call table whose previous asynchronous batch has not finished: a reader
+ * has three of each per device, taken in turn across calls, so this happens
+ * to a call of more than three batches and to a fourth batch (or call) in
+ * flight.
+ *
+ * Every synchronous read on the same reader (zseek_pread, zseek_read,
+ * zsk_pread_device, zsk_preadv, zsk_preadv_device) stays correct while
+ * asynchronous work is in flight: each first waits for what it needs.
+ * zseek_reader_close waits for all of the reader's queued work before it
+ * frees anything; @d_buf, @d_result and, for a device-image reader, the image
+ * must stay valid until the work has run.
+ */
+ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf,
+    const zsk_range_t *ranges, size_t nranges, int64_t *d_result, void *stream,
+    void *call_data, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 /*
  * The device-side building block, for callers of zsk_*_decode_frames: copy

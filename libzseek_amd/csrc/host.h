@@ -141,11 +141,40 @@ struct Slot {
     uint32_t seq = 0;
     bool flagged = false;
     volatile uint32_t *h_flag = nullptr;
+    // An asynchronous batch (zsk_preadv_device_async) was queued on the
+    // CALLER's stream and nobody has waited for it: `done` (recorded there
+    // behind its last command) has to pass before the host rewrites the
+    // slot's pinned staging, before reserve() may free a buffer and before
+    // any other stream touches its device buffers.  Stream order protects
+    // none of these, so every user of a slot calls drain() first.
+    bool pending = false;
+    void drain();
 
     bool reserve(size_t comp, size_t out, size_t host_out, size_t nframes, bool ck, char *errbuf);
     void destroy();
     size_t device_bytes() const;
     size_t host_bytes() const;
+};
+
+// What one asynchronous vectored read keeps for its whole duration (the
+// batches' slots are recycled under it): the per-call table of
+// range_result.h -- rows, then t_doff, uploaded from pinned staging -- and
+// behind it one int32 status per touched frame, which every batch appends to
+// and range_result_kernel reads.  Same lifetime rule as a slot: `done` is
+// recorded on the caller's stream behind the call's last command, and drain()
+// comes before the host rewrites `h` or either buffer is reallocated.
+struct CallTable {
+    hipEvent_t done = nullptr;
+    bool pending = false;
+    uint8_t *h = nullptr;   // pinned: the upload
+    size_t h_cap = 0;
+    void *h_dev = nullptr;  // its device mapping (upload_small)
+    uint8_t *d = nullptr;   // device: the upload, then the statuses
+    size_t d_cap = 0;
+
+    void drain();
+    bool reserve(size_t upload, size_t total, char *errbuf);   // (drained first)
+    void destroy();
 };
 
 // A reader's context on one device (a "lane"): kSlots batches in flight,
@@ -154,6 +183,11 @@ constexpr int kSlots = 3;
 struct DeviceCtx {
     int device = -1;
     Slot slot[kSlots];
+    // asynchronous reads: their batches take the slots round robin ACROSS
+    // calls (back-to-back calls of one batch each do not meet on slot 0), and
+    // as many calls' tables may be in flight
+    CallTable call[kSlots];
+    int async_slot = 0, async_call = 0;
     uint64_t batches = 0, frames_decoded = 0, bytes_decoded = 0, bytes_uploaded = 0;
 
     DeviceCtx() = default;

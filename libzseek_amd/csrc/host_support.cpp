@@ -485,8 +485,17 @@ bool grow_host(T **p, size_t *cap, size_t want_elems)
 }
 }   // namespace
 
+void Slot::drain()
+{
+    if (!pending)
+        return;
+    (void)hipEventSynchronize(done);
+    pending = false;
+}
+
 bool Slot::reserve(size_t comp, size_t out, size_t host_out, size_t nframes, bool ck, char *errbuf)
 {
+    drain();   // (its users drained it already: nothing is freed under a batch in flight)
     if (!grow_dev(&d_comp, &d_comp_cap, comp) || !grow_dev(&d_out, &d_out_cap, out) ||
         !grow_dev(&d_status, &d_status_cap, 2 * nframes) ||
         (ck && !grow_dev(&d_ck, &d_ck_cap, nframes))) {
@@ -527,6 +536,7 @@ void Slot::destroy()
 {
     if (!stream)
         return;
+    drain();   // an asynchronous batch on a caller's stream
     (void)hipStreamSynchronize(stream);
     pool_wait(&copies);
     zstd_scratch_release_memory(&zs);
@@ -554,6 +564,53 @@ void Slot::destroy()
     d_comp_cap = d_out_cap = d_status_cap = d_ck_cap = 0;
 }
 
+void CallTable::drain()
+{
+    if (!pending)
+        return;
+    (void)hipEventSynchronize(done);
+    pending = false;
+}
+
+bool CallTable::reserve(size_t upload, size_t total, char *errbuf)
+{
+    drain();
+    if (!done && hip_event_get(&done) != hipSuccess) {
+        done = nullptr;
+        set_error(errbuf, "create HIP stream failed");
+        return false;
+    }
+    if (!grow_dev(&d, &d_cap, total)) {
+        set_error(errbuf, "allocate GPU decode buffers failed");
+        return false;
+    }
+    const void *const h0 = h;
+    if (!grow_host(&h, &h_cap, upload)) {
+        set_error(errbuf, "allocate pinned staging failed");
+        return false;
+    }
+    if (h != h0 || (h && !h_dev)) {
+        h_dev = nullptr;
+        if (h && hipHostGetDevicePointer(&h_dev, h, 0) != hipSuccess)
+            h_dev = nullptr;
+    }
+    return true;
+}
+
+void CallTable::destroy()
+{
+    drain();
+    if (d)
+        (void)hipFree(d);
+    if (h)
+        (void)hipHostFree(h);
+    hip_event_put(done);
+    done = nullptr;
+    d = h = nullptr;
+    h_dev = nullptr;
+    d_cap = h_cap = 0;
+}
+
 size_t Slot::device_bytes() const
 {
     return d_comp_cap + d_out_cap + (d_status_cap + d_ck_cap) * 4 +
@@ -571,6 +628,9 @@ DeviceCtx::~DeviceCtx()
         return;
     DeviceGuard keep;
     (void)hipSetDevice(device);
+    // (a call's last command is behind its batches': the tables first)
+    for (CallTable &c : call)
+        c.destroy();
     for (Slot &s : slot)
         s.destroy();
 }
@@ -605,6 +665,8 @@ size_t DeviceCtx::device_bytes() const
     size_t n = 0;
     for (const Slot &s : slot)
         n += s.device_bytes();
+    for (const CallTable &c : call)
+        n += c.d_cap;
     return n;
 }
 
@@ -613,6 +675,8 @@ size_t DeviceCtx::host_bytes() const
     size_t n = 0;
     for (const Slot &s : slot)
         n += s.host_bytes();
+    for (const CallTable &c : call)
+        n += c.h_cap;
     return n;
 }
 

@@ -57,6 +57,7 @@
 #include "lane_plan.h"
 #include "pool.h"
 #include "range_plan.h"
+#include "range_result.h"
 
 using namespace zsk;
 
@@ -309,8 +310,11 @@ extern "C" ZSEEK_EXPORT bool zseek_reader_close(zseek_reader_t *reader, void *ca
     (void)errbuf;
     if (!reader)
         return true;   // ref decompress.c:362-363
+    // the lanes first: their teardown waits for every batch an asynchronous
+    // read left queued on a caller's stream (Slot::drain, CallTable::drain)
+    // before anything they read is freed
+    reader->lanes.clear();
     if (DeviceImage *img = reader->img) {
-        // (every read is synchronous: nothing of the lanes still reads the table)
         DeviceGuard keep;
         if (img->d_table && hipSetDevice(img->device) == hipSuccess)
             (void)hipFree(img->d_table);
@@ -583,6 +587,7 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     if (!J.cache_cap && !ck && J.end < st.d_off[f1])
         stop_last = (uint32_t)(J.end - st.d_off[f1 - 1]);
     (void)hipSetDevice(g.device);
+    s.drain();   // an asynchronous read's batch may still be using the slot
     // the host copies of this slot's previous batch read its pinned bounce
     // h_out: wait for them only when reserve() will reallocate it (waiting
     // always serialized each batch's host copy with the next batch's read
@@ -1142,9 +1147,20 @@ struct VecJob {
     bool device_dst = false;
     std::vector<int32_t> status;     // per touched frame (P->frames)
     std::vector<uint32_t> fail_at;
+    // zsk_preadv_device_async: the batch's commands go on the caller's stream
+    // `q` (NULL: the null stream) and nobody waits for them; its statuses are
+    // appended on that stream to d_call_status (per touched frame, the call's
+    // CallTable) instead of downloaded, and there is no finish_gather
+    bool async = false;
+    hipStream_t q = nullptr;
+    int32_t *d_call_status = nullptr;
 };
 
-// Read, upload, decode and gather batch bi on slot s.
+// Read, upload, decode and gather batch bi on slot s.  Asynchronous mode
+// (V.async): everything is queued on the caller's stream, directly -- the
+// slot's own stream is not used, so "stream-ordered" needs no event bridge --
+// and the slot is left `pending` behind its `done` event for its next user
+// to drain.
 bool submit_gather(VecJob &V, Slot &s, size_t bi)
 {
     zseek_reader *r = V.J.r;
@@ -1166,6 +1182,11 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     const uint64_t h_len = V.device_dst ? 0 : b.out_bytes;
     const uint64_t pack_at = (dsz + 255) & ~255ull;
     (void)hipSetDevice(g.device);
+    // the slot's previous asynchronous batch must have finished before the
+    // host rewrites its pinned staging below (a host wait, the one a fourth
+    // batch in flight costs)
+    s.drain();
+    hipStream_t const q = V.async ? V.q : s.stream;
     if (h_len > s.h_out_cap)
         pool_wait(&s.copies);
     // a file in device memory: nothing is read or packed -- the touched frames
@@ -1237,28 +1258,28 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     const bool wave = r->type == ZSEEK_LZ4 && lz4_pick_engine((uint32_t)n) == ENGINE_WAVE;
     hipError_t e = hipSuccess;
     if (host_dma)
-        e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, s.stream);
-    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, s.stream) != 0)
+        e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, q);
+    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, q) != 0)
         e = hipErrorLaunchFailure;
     if (e == hipSuccess && wave)
-        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, n, s.stream);
+        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, n, q);
     if (e == hipSuccess && wave)
-        e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, n, s.stream);
+        e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, n, q);
     if (e == hipSuccess && r->type == ZSEEK_ZSTD &&
         (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
-                                            (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
+                                            (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, q, d_fail,
                                             stop_last)
-               : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
+               : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs, q, d_fail,
                                     stop_last)) != 0)
         e = hipErrorLaunchFailure;
     if (e == hipSuccess && r->type == ZSEEK_LZ4) {
         if (wave) {
-            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
+            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, q) != 0)
                 e = hipErrorLaunchFailure;
         } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
-                                         s.stream) != 0) {
+                                         q) != 0) {
             e = hipErrorOutOfMemory;
-        } else if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
+        } else if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, q, &s.split,
                                     ROUTE_AUTO, 15, 0, stop_last, max_dsize, nullptr, nullptr, true) != 0) {
             e = hipErrorLaunchFailure;
         }
@@ -1266,9 +1287,9 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     if (e == hipSuccess && ck) {
         for (size_t i = 0; i < n; i++)
             s.h_ck[i] = st.checksum[P.frames[b.t0 + i]];
-        e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
+        e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, q);
         if (e == hipSuccess &&
-            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, s.d_ck, s.d_status, s.stream) != 0)
+            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, s.d_ck, s.d_status, q) != 0)
             e = hipErrorLaunchFailure;
     }
     // the segments of the frames that decoded: into the caller's device
@@ -1281,22 +1302,34 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
         uint8_t *const dst = V.device_dst ? V.buf : mapped ? static_cast<uint8_t *>(s.h_out_dev) : s.d_out + pack_at;
         if (launch_range_gather(reinterpret_cast<const GatherSeg *>(s.d_comp + goff),
                                 reinterpret_cast<const uint64_t *>(s.d_comp + coff), (uint32_t)nseg, b.out_bytes,
-                                s.d_out, dst, s.d_status, s.stream) != 0)
+                                s.d_out, dst, s.d_status, q) != 0)
             e = hipErrorLaunchFailure;
         if (e == hipSuccess && h_len && !mapped)
-            e = hipMemcpyAsync(s.h_out, s.d_out + pack_at, h_len, hipMemcpyDeviceToHost, s.stream);
+            e = hipMemcpyAsync(s.h_out, s.d_out + pack_at, h_len, hipMemcpyDeviceToHost, q);
     }
-    if (e == hipSuccess &&
-        download_small(reinterpret_cast<uint32_t *>(s.h_status), host_dma ? nullptr : s.h_status_dev,
-                       reinterpret_cast<const uint32_t *>(s.d_status), (uint32_t)(2 * n), nullptr, nullptr, s.d_out, 0,
-                       s.stream) != 0)
+    // the statuses: downloaded for finish_gather, or (asynchronous) kept on the
+    // device, appended to the call's, which outlive the slot's reuse by a later
+    // batch (a range can span batches)
+    if (e == hipSuccess && V.async)
+        e = hipMemcpyAsync(V.d_call_status + b.t0, s.d_status, n * sizeof(int32_t), hipMemcpyDeviceToDevice, q);
+    else if (e == hipSuccess &&
+             download_small(reinterpret_cast<uint32_t *>(s.h_status), host_dma ? nullptr : s.h_status_dev,
+                            reinterpret_cast<const uint32_t *>(s.d_status), (uint32_t)(2 * n), nullptr, nullptr,
+                            s.d_out, 0, q) != 0)
         e = hipErrorLaunchFailure;
-    if (e == hipSuccess)
-        e = hipEventRecord(s.done, s.stream);
+    // (asynchronous: whatever was queued, a failed batch's part included, is
+    // behind `done`; the slot's next user waits for it, this call does not)
+    if (e == hipSuccess || V.async) {
+        const hipError_t er = hipEventRecord(s.done, q);
+        s.pending = V.async && er == hipSuccess;
+        if (e == hipSuccess)
+            e = er;
+    }
     if (e != hipSuccess) {
         set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
         V.J.io_failed = true;
-        (void)hipStreamSynchronize(s.stream);
+        if (!s.pending)
+            (void)hipStreamSynchronize(q);
         return false;
     }
     g.batches++;
@@ -1455,6 +1488,195 @@ ssize_t preadv_frames(zseek_reader *r, void *buf, zsk_range_t *ranges, size_t nr
         }
     }
     return (ssize_t)ok;
+}
+
+// An asynchronous call grows buffers for ALL of the lane's idle slots and call
+// tables at once, to what its largest batch needs (submit_gather's sizes, LZ4
+// with a device destination): growing waits for the device, and a slot grown
+// only when a later call reaches it would make that call wait for the caller's
+// stream in the middle of a pipeline that the first call had warmed up.  Slots
+// and tables with work in flight are left alone (their turn comes after their
+// drain).  Best effort: a failure here is reported by the batch that needs
+// the buffer.
+void grow_idle_for_async(VecJob &V, DeviceCtx &g, size_t table_up, size_t table_total)
+{
+    zseek_reader *r = V.J.r;
+    const SeekTable &st = r->st;
+    const RangePlan &P = *V.P;
+    const DeviceImage *const img = r->img;
+    const bool ck = r->verify && st.checksum_flag;
+    uint64_t up = 0, out = 0, items = 0;
+    size_t nmax = 0;
+    std::vector<FrameDesc> desc;
+    for (const PlanBatch &b : P.batches) {
+        const size_t n = b.t1 - b.t0, nseg = b.s1 - b.s0;
+        desc.resize(n);
+        uint64_t c = 0;
+        for (size_t i = 0; i < n; i++) {
+            const size_t f = P.frames[b.t0 + i];
+            desc[i].c_off = img ? st.c_off[f] + img->bias : c;
+            desc[i].c_size = (uint32_t)st.csize(f);
+            c += desc[i].c_size;
+        }
+        const uint64_t doff = img ? 0 : (c + 256 + 255) & ~255ull;
+        up = std::max<uint64_t>(up, doff + n * sizeof(FrameDesc) + nseg * sizeof(GatherSeg) +
+                                        (nseg + 1) * sizeof(uint64_t));
+        out = std::max<uint64_t>(out, (b.d_bytes + 255) & ~255ull);
+        items = std::max(items, split_items_needed(desc.data(), (uint32_t)n));
+        nmax = std::max(nmax, n);
+    }
+    const bool split = lz4_pick_engine((uint32_t)nmax) != ENGINE_WAVE;
+    char err[ZSEEK_ERRBUF_SIZE];
+    for (Slot &s : g.slot) {
+        if (s.pending || !nmax)
+            continue;
+        (void)s.reserve(up, out, 0, nmax, ck, err);
+        // (on the slot's own, idle stream: its wait is no wait; the scratch's
+        // first memset is complete before the caller's stream uses it)
+        if (split && split_scratch_reserve(&s.split, (uint32_t)nmax, items, s.stream) == 0)
+            (void)hipStreamSynchronize(s.stream);
+        (void)hipGetLastError();
+    }
+    for (CallTable &c : g.call)
+        if (!c.pending)
+            (void)c.reserve(table_up, table_total, err);
+}
+
+// zsk_preadv_device_async (zseek_hip.h): preadv_frames' batches queued on the
+// caller's stream, one after the other, and behind the last one
+// range_result_kernel, which leaves in d_result what range_results computes on
+// the host.  Nothing is waited for except a slot or a call table that an
+// earlier asynchronous batch still uses (Slot::drain, CallTable::drain) and
+// buffers that have to grow.
+ssize_t preadv_async(zseek_reader *r, void *d_buf, const zsk_range_t *ranges, size_t nranges, int64_t *d_result,
+                     hipStream_t q, void *call_data, char *errbuf)
+{
+    if (!r) {
+        set_error(errbuf, "invalid reader");
+        return -1;
+    }
+    // the call reuses pinned staging that the host rewrites: it must never
+    // end up in a graph
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(q, &cap);
+    if ((ce == hipSuccess && cap != hipStreamCaptureStatusNone) || ce == hipErrorStreamCaptureImplicit) {
+        (void)hipGetLastError();
+        set_error(errbuf, "asynchronous read: stream is capturing");
+        return -1;
+    }
+    (void)hipGetLastError();   // (no device: reported below, where one is needed)
+    if (r->type != ZSEEK_LZ4) {
+        // zsk_zstd_decode_frames' plan synchronizes
+        set_error(errbuf, "asynchronous read: zstd is not supported");
+        return -1;
+    }
+    if (nranges == 0 && !d_result)
+        return 0;
+    if (!ranges && nranges) {
+        set_error(errbuf, "invalid ranges");
+        return -1;
+    }
+    if (!d_result) {
+        set_error(errbuf, "invalid result buffer");
+        return -1;
+    }
+    const SeekTable &st = r->st;
+    std::vector<RangeReq> req(nranges);
+    for (size_t i = 0; i < nranges; i++)
+        req[i] = {ranges[i].offset, ranges[i].count, ranges[i].dst_off};
+    DeviceGuard keep_device;
+    std::unique_lock<std::shared_mutex> guard(r->lock);
+    struct Publish {
+        zseek_reader *r;
+        ~Publish() { publish_stats(r); }
+    } publish{r};
+    const size_t nframes = st.frames();
+    const uint64_t zero = 0;
+    const uint64_t *const d_off = nframes ? st.d_off.data() : &zero;
+    // (the batches are preadv_frames': see there for the device image's span cut)
+    const RangePlan P = r->img && nframes ? plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes,
+                                                        st.c_off.data(), (uint64_t)std::min<size_t>(r->batch_bytes, SIZE_MAX / 4) * 4)
+                                          : plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
+    if (!d_buf && !P.segs.empty()) {
+        set_error(errbuf, "invalid buffer");
+        return -1;
+    }
+    for (const PlanBatch &b : P.batches)
+        if (b.s1 - b.s0 >= 0xFFFFFFFFull || b.t1 - b.t0 >= 0x7FFFFFFFull) {
+            set_error(errbuf, "too many ranges");
+            return -1;
+        }
+    if (!ensure_lanes(r, errbuf))
+        return -1;
+    DeviceCtx &g = *r->lanes[0];
+    (void)hipSetDevice(g.device);
+    if (nranges == 0) {   // d_result[0] = 0 alone
+        if (launch_range_result(nullptr, nullptr, nullptr, 0, d_result, q) == 0)
+            return 0;
+        set_error(errbuf, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    // From here on a failure still leaves the stream's consumer an answer:
+    // every result and the count -1.
+    VecJob V;
+    V.P = &P;
+    V.buf = static_cast<uint8_t *>(d_buf);
+    V.device_dst = true;
+    V.async = true;
+    V.q = q;
+    V.J.r = r;
+    V.J.g = &g;
+    V.J.call_data = call_data;
+    CallTable &c = g.call[g.async_call];
+    g.async_call = (g.async_call + 1) % kSlots;
+    const size_t T = P.frames.size();
+    // rows, t_doff (the upload, which moves whole 16-byte pieces), statuses
+    const size_t rows_bytes = nranges * sizeof(RangeRow), up = rows_bytes + T * sizeof(uint64_t);
+    const size_t st_at = (up + 15) & ~(size_t)15;
+    grow_idle_for_async(V, g, up, st_at + T * sizeof(int32_t));
+    // (a host wait when this table's previous call, kSlots calls ago, has not
+    // finished: the host rewrites its pinned staging)
+    bool ok = c.reserve(up, st_at + T * sizeof(int32_t), V.J.err);
+    hipError_t e = hipSuccess;
+    if (ok) {
+        const RangeTable tab = build_range_table(P, req.data(), nranges, d_off, nframes);
+        memcpy(c.h, tab.rows.data(), rows_bytes);
+        if (T)
+            memcpy(c.h + rows_bytes, tab.t_doff.data(), T * sizeof(uint64_t));
+        V.d_call_status = reinterpret_cast<int32_t *>(c.d + st_at);
+        if (upload_small(c.d, c.h, c.h_dev, up, q) != 0)
+            e = hipErrorLaunchFailure;
+        // a batch that is never queued reads as failed
+        if (e == hipSuccess && T)
+            e = hipMemsetD32Async((hipDeviceptr_t)V.d_call_status, ST_NOT_RUN, T, q);
+        if (e != hipSuccess) {
+            set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
+            ok = false;
+        }
+    }
+    // the batches take the lane's slots round robin; a slot whose earlier
+    // asynchronous batch is still in flight is waited for (submit_gather)
+    for (size_t bi = 0; ok && bi < P.batches.size(); bi++) {
+        Slot &s = g.slot[g.async_slot];
+        g.async_slot = (g.async_slot + 1) % kSlots;
+        ok = submit_gather(V, s, bi);
+    }
+    if (ok && launch_range_result(reinterpret_cast<const RangeRow *>(c.d),
+                                  reinterpret_cast<const uint64_t *>(c.d + rows_bytes), V.d_call_status, nranges,
+                                  d_result, q) != 0) {
+        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
+        ok = false;
+    }
+    if (!ok)
+        (void)hipMemsetAsync(d_result, 0xFF, (nranges + 1) * sizeof(int64_t), q);
+    // the table is in use until the stream passes this point
+    if (c.done && !(c.pending = hipEventRecord(c.done, q) == hipSuccess))
+        (void)hipStreamSynchronize(q);
+    if (!ok) {
+        set_error(errbuf, "%s", V.J.err);
+        return -1;
+    }
+    return 0;
 }
 
 }   // namespace
@@ -1633,6 +1855,14 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *
                                                   size_t nranges, void *call_data, char *errbuf)
 {
     return preadv_frames(reader, d_buf, ranges, nranges, call_data, errbuf, true);
+}
+
+extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf, const zsk_range_t *ranges,
+                                                        size_t nranges, int64_t *d_result, void *stream,
+                                                        void *call_data, char *errbuf)
+{
+    return preadv_async(reader, d_buf, ranges, nranges, d_result, static_cast<hipStream_t>(stream), call_data,
+                        errbuf);
 }
 
 extern "C" ZSEEK_EXPORT int zsk_gather_segments(const zsk_segment_t *d_seg, uint32_t nseg, const void *d_src,

@@ -462,6 +462,15 @@ static_assert(sizeof(GatherSeg) == 24, "GatherSeg is part of the C ABI");
 int launch_range_gather(const GatherSeg *d_seg, const uint64_t *d_cum, uint32_t nseg, uint64_t total,
                         const uint8_t *d_src, uint8_t *d_dst, const int32_t *d_status, hipStream_t stream);
 
+// Per-range results of a vectored read on the device (range_result.hip; the
+// table and the arithmetic: range_result.h): d_result[r] for each of the n
+// rows from d_status[t] of the call's touched frames, and in d_result[n] the
+// number of ranges delivered in full (zeroed on the stream first).  n == 0
+// writes d_result[0] = 0 alone.  Asynchronous on stream; 0 or -1.
+struct RangeRow;
+int launch_range_result(const RangeRow *d_rows, const uint64_t *d_tdoff, const int32_t *d_status, uint64_t n,
+                        int64_t *d_result, hipStream_t stream);
+
 // Seek-table checksums (frame_check.hip): frames whose status is ST_OK and
 // whose decoded bytes' XXH64 low 32 bits differ from d_want[f] get
 // ST_SEEK_CHECKSUM.

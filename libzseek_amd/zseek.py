@@ -110,7 +110,7 @@ EXPORTED = [
     "zsk_verify_frame_checksums", "zsk_reader_set_verify_checksums",
     "zsk_reader_set_devices", "zsk_reader_devices", "zsk_reader_set_io_threads",
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
-    "zsk_preadv", "zsk_preadv_device", "zsk_gather_segments",
+    "zsk_preadv", "zsk_preadv_device", "zsk_preadv_device_async", "zsk_gather_segments",
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
 ]
@@ -201,6 +201,9 @@ def lib() -> C.CDLL:
     for fn in (L.zsk_preadv, L.zsk_preadv_device):
         fn.restype = C.c_ssize_t
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p]
+    L.zsk_preadv_device_async.restype = C.c_ssize_t
+    L.zsk_preadv_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_char_p]
     L.zsk_gather_segments.restype = C.c_int
     L.zsk_gather_segments.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
@@ -552,6 +555,20 @@ class Reader:
         if n_ok < 0:
             raise ZseekError(self.error)
         return rg, n_ok
+
+    def preadv_device_async(self, dev_ptr: int, ranges, result_ptr: int, stream: int = 0) -> None:
+        """zsk_preadv_device_async: preadv_device queued on `stream` (a
+        hipStream_t as an integer, e.g. torch.cuda.Stream.cuda_stream; 0: the
+        null stream) without waiting for it.  `ranges` as for preadv_device;
+        `result_ptr`: device memory of len(ranges) + 1 int64 -- each range's
+        result, then the number of ranges delivered in full, valid once the
+        stream has run the call's work.  ZseekError when the call itself
+        fails (the results are then all -1)."""
+        rg = self._ranges(ranges)
+        ret = lib().zsk_preadv_device_async(self._h, dev_ptr, rg.ctypes.data if rg.size else None, rg.size,
+                                            result_ptr, stream, None, self._err)
+        if ret < 0:
+            raise ZseekError(self.error)
 
     def stats(self) -> dict:
         s = ReaderStatsC()
