@@ -24,6 +24,9 @@
  *                            its device-side segmented copy.
  *   zsk_preadv_device_async — the same read queued on the caller's stream,
  *                            its per-range results left in device memory.
+ *   zsk_preadv_device_indirect — ... with the range list in device memory
+ *                            too, planned by kernels from the seek table a
+ *                            device-image reader keeps resident.
  *   zsk_verify_frame_checksums — the seek table's per-frame checksum,
  *                            parsed by seek_table.c:95-97 and never checked
  *                            there, checked on the GPU.
@@ -287,6 +290,96 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf,
 ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf,
     const zsk_range_t *ranges, size_t nranges, int64_t *d_result, void *stream,
     void *call_data, char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * zsk_preadv_device_async for a range list that is itself in DEVICE memory,
+ * on a reader over a device image (zsk_reader_open_device, LZ4): the plan --
+ * which frames the ranges touch, their descriptors, the (range, frame)
+ * segments -- is computed by kernels on @stream from the seek table the
+ * reader keeps on the device, so ranges produced on the GPU (a sampler, an
+ * index lookup, an earlier read) never visit the host.  Nothing but the
+ * call's arguments goes host -> device, no pinned staging is rewritten, and
+ * the host waits only as listed below.
+ *
+ * @d_ranges: @nranges zsk_range_t in device memory, read on @stream: work
+ * queued on @stream before the call may have written them; they must stay
+ * valid until the stream has passed the call's work; their `result` fields
+ * are never written.  @d_result: nranges + 1 int64_t in device memory.
+ * @d_buf[0, buf_size): the destination.
+ *
+ * When the stream reaches the end of the call's work, d_result[i],
+ * d_result[nranges] and the bytes in @d_buf are exactly what
+ * zsk_preadv_device_async leaves for the same ranges on the same reader (the
+ * full count; short at EOF; 0 for an empty range or one at / past EOF; the
+ * bytes before the first failed frame; -1 when the first frame fails; in
+ * d_result[nranges] the ranges delivered in full).  Ranges may be unsorted,
+ * overlap in the source, share frames or repeat; destinations must be
+ * disjoint.  offset + count may wrap: the range ends at EOF.
+ *
+ * The list is data, not trusted input: a range whose destination [dst_off,
+ * dst_off + count) is not inside [0, buf_size) gets -1, moves no byte and is
+ * not counted as delivered.  A garbage list can produce wrong results; it can
+ * never make the call write outside d_buf[0, buf_size).
+ *
+ * @max_frames is the caller's bound on the distinct frames one call touches.
+ * The call is ONE batch: it reserves max_frames x (the file's largest frame
+ * dSize) of decoded staging and is refused up front when that exceeds the
+ * reader's batch size (zsk_reader_set_batch_bytes): -1, "device-planned
+ * read: max_frames frames exceed the batch size" (and, a segment's length
+ * being 32 bits, when it reaches 4 GiB: "... exceed 4 GiB").
+ *
+ * Segments: a host-planned read moves one segment per (range, frame)
+ * overlap, which nranges + max_frames slots hold for ranges that are disjoint
+ * in the source (sorted by offset, two neighbours share at most one frame and
+ * every other frame belongs to one range: at most touched frames + nranges -
+ * 1) but not for ranges that overlap or repeat.  This call needs no such
+ * bound: the frames a range touches lie back to back in the decoded staging,
+ * so a range is ONE segment, nranges in all, moved when the range's first
+ * frame decoded.  The bytes before the first failed frame are delivered as
+ * always; what is moved behind them stays inside the range's own destination,
+ * past its result, where bytes are unspecified.  No list of @nranges ranges
+ * can run out of segments.
+ *
+ * When the ranges touch more than max_frames frames, nothing is decoded or
+ * moved: @d_buf is untouched, every d_result[i] is -1 and d_result[nranges]
+ * is ZSK_PLAN_OVERFLOW.  When the
+ * compressed bytes from the first touched frame's start to the last one's end
+ * are 2 GiB (less 256 bytes) or more -- the parse kernels address a batch
+ * through 32-bit offsets -- the outcome is the same with ZSK_PLAN_SPAN; the
+ * check is made on the device per call, so a larger image works for every read
+ * that stays within 2 GiB.
+ *
+ * Honours zsk_reader_set_verify_checksums (the touched frames' words come
+ * from the resident table); neither consults nor fills the frame cache; holds
+ * the reader's exclusive lock for the enqueue only.  Counters: `batches`
+ * advances by 1 at enqueue; frames_decoded and bytes_decoded do NOT advance
+ * (the host never learns what the ranges touched); bytes_uploaded stays 0.
+ *
+ * -1 + errbuf and nothing queued for: a NULL reader ("invalid reader"); a
+ * reader not opened with zsk_reader_open_device ("device-planned read: needs
+ * a device image"); a zstd reader ("device-planned read: zstd is not
+ * supported"); a capturing stream ("device-planned read: stream is
+ * capturing"); nranges > 0 with NULL @d_ranges, NULL @d_result or max_frames
+ * == 0; nranges > 0, buf_size > 0 and NULL @d_buf ("invalid buffer"); the
+ * staging refusal above; a seek table that reaches past the image
+ * ("unexpected EOF").  nranges == 0 returns 0 and queues only d_result[0] = 0
+ * (nothing for a NULL @d_result).  A HIP failure after something was queued
+ * still queues a fill of d_result[0 .. nranges] with -1 and returns -1.
+ *
+ * Host waits the call may make: growing its buffers (first use, a larger
+ * call), and reusing one of the reader's three batch slots or call tables
+ * while an earlier asynchronous call still runs on it -- the slots and tables
+ * are taken in turn, as zsk_preadv_device_async takes them.  Synchronous
+ * reads on the same reader stay correct while such a call is in flight, and
+ * zseek_reader_close waits for it.  Not for a capturing stream; not for host
+ * images; a read of more than one batch is the caller's loop.
+ */
+#define ZSK_PLAN_OVERFLOW (-2)  /* more touched frames than the call reserved */
+#define ZSK_PLAN_SPAN     (-3)  /* the touched frames span 2 GiB or more of the image */
+ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *reader,
+    void *d_buf, size_t buf_size,
+    const zsk_range_t *d_ranges, size_t nranges, size_t max_frames,
+    int64_t *d_result, void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 /*
  * The device-side building block, for callers of zsk_*_decode_frames: copy

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void lz4_plan_direct_kernel(const FrameDesc *_
                                                                uint32_t *__restrict__ redo,
                                                                int32_t *__restrict__ status,
                                                                uint32_t *__restrict__ fail_at,
-                                                               BlockPlanArgs bp)
+                                                               BlockPlanArgs bp, uint32_t by_scan)
 {
     __shared__ uint64_t part[256];
     __shared__ uint32_t last;
@@ -204,6 +204,12 @@ __global__ __launch_bounds__(256) void lz4_plan_direct_kernel(const FrameDesc *_
     }
     if (n == 1)   // one frame is always in order
         return;
+    // by_scan: the caller's frames lie anywhere in the input (sparse frames of
+    // a device image, padding descriptors among them): the slots by the scan
+    // whatever their order, so the scratch they take is the sum of
+    // slots_of(c_size) and never the compressed distance they span
+    if (by_scan && threadIdx.x == 0)
+        atomicOr(&redo[0], 1u);
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
@@ -621,7 +627,7 @@ const char *parse_kernel_name(uint32_t nframes, uint32_t c_size, int route)
 int launch_lz4_split(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
                      uint8_t *d_out, int32_t *d_status, uint32_t *d_fail_at,
                      hipStream_t stream, SplitScratch *s, int route, int stages, int tune, uint32_t stop_last,
-                     uint32_t max_dsize, const HostPost *post, bool *posted, bool in_order)
+                     uint32_t max_dsize, const HostPost *post, bool *posted, bool in_order, bool scan_layout)
 {
     if (posted)
         *posted = false;
@@ -685,7 +691,7 @@ int launch_lz4_split(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d
         if (pgroups != 1)
             pbp.bfirst = nullptr;
         hipLaunchKernelGGL(lz4_plan_direct_kernel, dim3(pgroups), dim3(256), 0, stream, d_desc, nframes, s->rec_base,
-                           total_dev, s->redo, d_status, d_fail_at, pbp);
+                           total_dev, s->redo, d_status, d_fail_at, pbp, scan_layout ? 1u : 0u);
         if (blk && pgroups != 1)
             hipLaunchKernelGGL(lz4_block_plan_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, d_desc,
                                nframes, bp);

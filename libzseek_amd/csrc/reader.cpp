@@ -57,6 +57,7 @@
 #include "lane_plan.h"
 #include "pool.h"
 #include "range_plan.h"
+#include "range_plan_dev.h"
 #include "range_result.h"
 
 using namespace zsk;
@@ -86,6 +87,9 @@ struct DeviceImage {
     size_t table_bytes = 0;
     const uint64_t *d_coff = nullptr, *d_doff = nullptr;
     const uint32_t *d_ck = nullptr;
+    // the file's largest frame, decoded and compressed: what a device-planned
+    // read (preadv_indirect) sizes its staging and its parse scratch by
+    uint32_t max_dsize = 0, max_csize = 0;
 };
 
 struct zseek_reader {
@@ -282,6 +286,10 @@ extern "C" ZSEEK_EXPORT zseek_reader_t *zsk_reader_open_device(const void *d_ima
     r->devices.assign(1, img->device);
     // the table, once: a batch's descriptors and checksum words come from it
     const size_t n = r->st.frames();
+    for (size_t f = 0; f < n; f++) {
+        img->max_dsize = std::max(img->max_dsize, (uint32_t)r->st.dsize(f));
+        img->max_csize = std::max(img->max_csize, (uint32_t)r->st.csize(f));
+    }
     const size_t sums = r->st.checksum_flag ? n * sizeof(uint32_t) : 0;
     img->table_bytes = 2 * (n + 1) * sizeof(uint64_t) + sums;
     bool ok = !r->st.c_off.empty() && hipMalloc((void **)&img->d_table, img->table_bytes) == hipSuccess;
@@ -1679,6 +1687,165 @@ ssize_t preadv_async(zseek_reader *r, void *d_buf, const zsk_range_t *ranges, si
     return 0;
 }
 
+// zsk_preadv_device_indirect (zseek_hip.h): a vectored read of a device image
+// whose ranges are in device memory.  The plan is computed on the device
+// (range_plan_dev.hip) from the resident seek table; the host sizes every
+// buffer and grid by its bounds -- nranges, max_frames, the file's largest
+// frame -- and sends nothing but kernel arguments.  One batch: the touched
+// frames (at most max_frames, then padding descriptors) decoded in place from
+// the image into the slot's staging, gathered into d_buf, the results by
+// range_result_kernel and the plan's fix kernel.  The slot and the call table
+// are taken in turn and left pending like preadv_async's.
+ssize_t preadv_indirect(zseek_reader *r, void *d_buf, size_t buf_size, const zsk_range_t *d_ranges, size_t nranges,
+                        size_t max_frames, int64_t *d_result, hipStream_t q, char *errbuf)
+{
+    if (!r) {
+        set_error(errbuf, "invalid reader");
+        return -1;
+    }
+    const DeviceImage *const img = r->img;
+    if (!img) {
+        set_error(errbuf, "device-planned read: needs a device image");
+        return -1;
+    }
+    if (r->type != ZSEEK_LZ4) {
+        set_error(errbuf, "device-planned read: zstd is not supported");
+        return -1;
+    }
+    // (scratch sized per call and reused: never in a graph)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(q, &cap);
+    if ((ce == hipSuccess && cap != hipStreamCaptureStatusNone) || ce == hipErrorStreamCaptureImplicit) {
+        (void)hipGetLastError();
+        set_error(errbuf, "device-planned read: stream is capturing");
+        return -1;
+    }
+    (void)hipGetLastError();
+    if (nranges == 0 && !d_result)
+        return 0;
+    if (nranges && !d_ranges) {
+        set_error(errbuf, "invalid ranges");
+        return -1;
+    }
+    if (!d_result) {
+        set_error(errbuf, "invalid result buffer");
+        return -1;
+    }
+    if (nranges && max_frames == 0) {
+        set_error(errbuf, "device-planned read: max_frames is 0");
+        return -1;
+    }
+    if (nranges && buf_size && !d_buf) {
+        set_error(errbuf, "invalid buffer");
+        return -1;
+    }
+    // (the gather takes a 32-bit segment count, the decode a 31-bit frame count)
+    if (max_frames >= 0x7FFFFFFFull || nranges >= 0xFFFFFFFFull) {
+        set_error(errbuf, "too many ranges");
+        return -1;
+    }
+    const SeekTable &st = r->st;
+    DeviceGuard keep_device;
+    std::unique_lock<std::shared_mutex> guard(r->lock);
+    struct Publish {
+        zseek_reader *r;
+        ~Publish() { publish_stats(r); }
+    } publish{r};
+    if (nranges && img->max_dsize && max_frames > r->batch_bytes / img->max_dsize) {
+        set_error(errbuf, "device-planned read: max_frames frames exceed the batch size");
+        return -1;
+    }
+    // (a range is one segment of the staging, and a segment's length a u32)
+    if (nranges && (uint64_t)max_frames * img->max_dsize > 0xFFFFFFFFull) {
+        set_error(errbuf, "device-planned read: max_frames frames exceed 4 GiB");
+        return -1;
+    }
+    // (a table that puts frames past the image's end: image_span's refusal,
+    // once for the whole table -- its prefix sums only grow)
+    if (st.c_off.back() > img->size) {
+        set_error(errbuf, "unexpected EOF");
+        return -1;
+    }
+    if (!ensure_lanes(r, errbuf))
+        return -1;
+    DeviceCtx &g = *r->lanes[0];
+    (void)hipSetDevice(g.device);
+    if (nranges == 0) {   // d_result[0] = 0 alone
+        if (launch_range_result(nullptr, nullptr, nullptr, 0, d_result, q) == 0)
+            return 0;
+        set_error(errbuf, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    const size_t nframes = st.frames();
+    const bool ck = r->verify && st.checksum_flag;
+    const PlanLayout L = plan_layout(nranges, max_frames, nframes, ck);
+    const PlanTables T{img->d_coff, img->d_doff, ck ? img->d_ck : nullptr, nframes, img->bias};
+    const uint32_t M = (uint32_t)max_frames;
+    const bool wave = lz4_pick_engine(M) == ENGINE_WAVE;
+    Slot &s = g.slot[g.async_slot];
+    g.async_slot = (g.async_slot + 1) % kSlots;
+    CallTable &c = g.call[g.async_call];
+    g.async_call = (g.async_call + 1) % kSlots;
+    char err[ZSEEK_ERRBUF_SIZE] = {0};
+    // (host waits: a slot or table whose earlier asynchronous work has not
+    // finished, and buffers that have to grow)
+    s.drain();
+    bool ok = c.reserve(0, L.total, err) && s.reserve(0, std::max<size_t>((size_t)max_frames * img->max_dsize, 16), 0, max_frames, false, err);
+    // the parse scratch by the plan's scan layout: max_frames frames of at most
+    // the file's largest compressed size, however far apart they lie
+    if (ok && !wave && split_scratch_reserve(&s.split, M, (uint64_t)M * slots_of(img->max_csize), q) != 0) {
+        set_error(err, "allocate GPU decode buffers failed");
+        ok = false;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        set_error(errbuf, "%s", err);
+        return -1;   // (nothing queued)
+    }
+    // From here on a failure still leaves the stream's consumer an answer:
+    // every result and the count -1.
+    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(c.d + L.desc);
+    uint32_t *const d_fail = reinterpret_cast<uint32_t *>(s.d_status + M);
+    s.f0 = s.f1 = 0;
+    s.h_from = s.h_len = 0;
+    s.flagged = false;
+    ok = launch_indirect_plan(c.d, L, T, d_ranges, nranges, buf_size, max_frames, q) == 0;
+    if (ok && wave)
+        ok = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, M, q) == hipSuccess &&
+             hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, M, q) == hipSuccess &&
+             launch_lz4_wave(d_desc, M, img->base, s.d_out, s.d_status, d_fail, q) == 0;
+    else if (ok)
+        ok = launch_lz4_split(d_desc, M, img->base, s.d_out, s.d_status, d_fail, q, &s.split, ROUTE_AUTO, 15, 0,
+                              0xFFFFFFFFu, img->max_dsize, nullptr, nullptr, false, true) == 0;
+    if (ok && ck)
+        ok = launch_frame_checksums(d_desc, M, s.d_out, reinterpret_cast<const uint32_t *>(c.d + L.ck), s.d_status,
+                                    q) == 0;
+    // (no host total: the gather's scan launch reads the segments' on the device)
+    if (ok && d_buf)
+        ok = launch_range_gather(reinterpret_cast<const GatherSeg *>(c.d + L.segs), nullptr, (uint32_t)L.seg_cap, 0,
+                                 s.d_out, static_cast<uint8_t *>(d_buf), s.d_status, q) == 0;
+    if (ok)
+        ok = launch_range_result(reinterpret_cast<const RangeRow *>(c.d + L.rows),
+                                 reinterpret_cast<const uint64_t *>(c.d + L.t_doff), s.d_status, nranges, d_result,
+                                 q) == 0 &&
+             launch_indirect_fix(c.d, L, nranges, d_result, q) == 0;
+    if (!ok) {
+        set_error(err, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipMemsetAsync(d_result, 0xFF, (nranges + 1) * sizeof(int64_t), q);
+    }
+    // the slot and the table are in use until the stream passes this point
+    s.pending = hipEventRecord(s.done, q) == hipSuccess;
+    c.pending = s.pending && hipEventRecord(c.done, q) == hipSuccess;
+    if (!s.pending || !c.pending)
+        (void)hipStreamSynchronize(q);
+    if (!ok) {
+        set_error(errbuf, "%s", err);
+        return -1;
+    }
+    g.batches++;   // (frames_decoded / bytes_decoded: the host never learns them)
+    return 0;
+}
+
 }   // namespace
 
 // ---------------------------------------------------------------------------
@@ -1863,6 +2030,15 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, 
 {
     return preadv_async(reader, d_buf, ranges, nranges, d_result, static_cast<hipStream_t>(stream), call_data,
                         errbuf);
+}
+
+extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *reader, void *d_buf, size_t buf_size,
+                                                           const zsk_range_t *d_ranges, size_t nranges,
+                                                           size_t max_frames, int64_t *d_result, void *stream,
+                                                           char *errbuf)
+{
+    return preadv_indirect(reader, d_buf, buf_size, d_ranges, nranges, max_frames, d_result,
+                           static_cast<hipStream_t>(stream), errbuf);
 }
 
 extern "C" ZSEEK_EXPORT int zsk_gather_segments(const zsk_segment_t *d_seg, uint32_t nseg, const void *d_src,

@@ -173,13 +173,18 @@ int launch_lz4_split(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d
                      uint8_t *d_out, int32_t *d_status, uint32_t *d_fail_at,
                      hipStream_t stream, SplitScratch *s, int route = ROUTE_AUTO, int stages = 15,
                      int tune = 0, uint32_t stop_last = 0xFFFFFFFFu, uint32_t max_dsize = 0xFFFFFFFFu,
-                     const HostPost *post = nullptr, bool *posted = nullptr, bool in_order = false);
+                     const HostPost *post = nullptr, bool *posted = nullptr, bool in_order = false,
+                     bool scan_layout = false);
 // (in_order: the caller laid the frames out in order in d_comp -- the
 // one-frame route's chunk parse then does the plan's work, no plan launch.
 // max_dsize: the batch's largest decoded frame when the caller knows it --
 // the one-frame route then skips the wave execute for frames of <= 64 KiB.
 // post: a one-frame batch's results to the host from its execute, when the
-// batch takes that route (*posted = true; else the caller downloads))
+// batch takes that route (*posted = true; else the caller downloads).
+// scan_layout: the plan lays the item slots out by its scan of
+// slots_of(c_size) whatever the frames' order -- frames scattered over a
+// device image then take sum(slots_of(c_size)) slots, not the compressed
+// distance they span / 8; not with in_order)
 
 // Item slots of a frame in the split decoder's scratch.  An item is 8 bytes;
 // a sequence takes one (two when extended), a stored block two.  LZ4 data
@@ -470,6 +475,22 @@ int launch_range_gather(const GatherSeg *d_seg, const uint64_t *d_cum, uint32_t 
 struct RangeRow;
 int launch_range_result(const RangeRow *d_rows, const uint64_t *d_tdoff, const int32_t *d_status, uint64_t n,
                         int64_t *d_result, hipStream_t stream);
+
+// The device plan of zsk_preadv_device_indirect (range_plan_dev.hip; the
+// arithmetic and the buffer's layout: range_plan_dev.h): from n zsk_range_t in
+// device memory and the resident seek table to max_frames descriptors (the
+// touched frames in file order, then padding), the rows and t_doff of
+// launch_range_result, the checksum words and one segment per range in d_plan
+// (L.total bytes, its head zeroed on the stream first).  launch_indirect_fix
+// goes behind launch_range_result: a flagged call's results (-1 each, the
+// flag as the count), -1 for a range whose destination is outside the buffer.
+// Asynchronous on stream; 0 or -1.
+struct PlanLayout;
+struct PlanTables;
+int launch_indirect_plan(uint8_t *d_plan, const PlanLayout &L, const PlanTables &T, const void *d_ranges, uint64_t n,
+                         uint64_t buf_size, uint64_t max_frames, hipStream_t stream);
+int launch_indirect_fix(const uint8_t *d_plan, const PlanLayout &L, uint64_t n, int64_t *d_result,
+                        hipStream_t stream);
 
 // Seek-table checksums (frame_check.hip): frames whose status is ST_OK and
 // whose decoded bytes' XXH64 low 32 bits differ from d_want[f] get

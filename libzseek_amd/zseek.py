@@ -98,6 +98,10 @@ assert RANGE_DTYPE.itemsize == 32
 SEGMENT_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("len", "<u4"), ("frame", "<u4")])
 assert SEGMENT_DTYPE.itemsize == 24
 
+# zsk_preadv_device_indirect: d_result[nranges] of a call that moved nothing
+PLAN_OVERFLOW = -2
+PLAN_SPAN = -3
+
 # exported C symbols that include/zseek.h and include/zseek_hip.h declare
 EXPORTED = [
     "zseek_writer_open_full", "zseek_writer_open", "zseek_writer_close", "zseek_write",
@@ -110,7 +114,8 @@ EXPORTED = [
     "zsk_verify_frame_checksums", "zsk_reader_set_verify_checksums",
     "zsk_reader_set_devices", "zsk_reader_devices", "zsk_reader_set_io_threads",
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
-    "zsk_preadv", "zsk_preadv_device", "zsk_preadv_device_async", "zsk_gather_segments",
+    "zsk_preadv", "zsk_preadv_device", "zsk_preadv_device_async", "zsk_preadv_device_indirect",
+    "zsk_gather_segments",
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
 ]
@@ -204,6 +209,9 @@ def lib() -> C.CDLL:
     L.zsk_preadv_device_async.restype = C.c_ssize_t
     L.zsk_preadv_device_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_char_p]
+    L.zsk_preadv_device_indirect.restype = C.c_ssize_t
+    L.zsk_preadv_device_indirect.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_char_p]
     L.zsk_gather_segments.restype = C.c_int
     L.zsk_gather_segments.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
@@ -567,6 +575,20 @@ class Reader:
         rg = self._ranges(ranges)
         ret = lib().zsk_preadv_device_async(self._h, dev_ptr, rg.ctypes.data if rg.size else None, rg.size,
                                             result_ptr, stream, None, self._err)
+        if ret < 0:
+            raise ZseekError(self.error)
+
+    def preadv_device_indirect(self, dev_ptr: int, buf_size: int, ranges_ptr: int, nranges: int, max_frames: int,
+                               result_ptr: int, stream: int = 0) -> None:
+        """zsk_preadv_device_indirect (a reader from open_device): the read of
+        preadv_device_async for `nranges` RANGE_DTYPE entries that are in device
+        memory at `ranges_ptr`, planned on the GPU and queued on `stream`.
+        `dev_ptr`, `buf_size`: the destination; `max_frames`: the caller's
+        bound on the frames the ranges touch; `result_ptr`: device memory of
+        nranges + 1 int64 (the last: the ranges delivered in full, or
+        PLAN_OVERFLOW / PLAN_SPAN).  ZseekError when the call itself fails."""
+        ret = lib().zsk_preadv_device_indirect(self._h, dev_ptr, buf_size, ranges_ptr, nranges, max_frames,
+                                               result_ptr, stream, self._err)
         if ret < 0:
             raise ZseekError(self.error)
 
