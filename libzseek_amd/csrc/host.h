@@ -150,6 +150,16 @@ struct Slot {
     bool pending = false;
     void drain();
 
+    // a new batch takes the slot: frames [f0, f1) (a vectored batch: none),
+    // h_len bytes from h_from of its span for the host, no completion flag yet
+    void begin_batch(size_t first, size_t end, uint64_t from, uint64_t len)
+    {
+        f0 = first;
+        f1 = end;
+        h_from = from;
+        h_len = len;
+        flagged = false;
+    }
     bool reserve(size_t comp, size_t out, size_t host_out, size_t nframes, bool ck, char *errbuf);
     void destroy();
     size_t device_bytes() const;
@@ -190,6 +200,26 @@ struct DeviceCtx {
     int async_slot = 0, async_call = 0;
     uint64_t batches = 0, frames_decoded = 0, bytes_decoded = 0, bytes_uploaded = 0;
 
+    Slot &take_slot()
+    {
+        Slot &s = slot[async_slot];
+        async_slot = (async_slot + 1) % kSlots;
+        return s;
+    }
+    CallTable &take_call()
+    {
+        CallTable &c = call[async_call];
+        async_call = (async_call + 1) % kSlots;
+        return c;
+    }
+    // one more batch queued (a device-planned read: frames and bytes unknown, 0)
+    void count_batch(uint64_t frames = 0, uint64_t decoded = 0, uint64_t uploaded = 0)
+    {
+        batches++;
+        frames_decoded += frames;
+        bytes_decoded += decoded;
+        bytes_uploaded += uploaded;
+    }
     DeviceCtx() = default;
     DeviceCtx(const DeviceCtx &) = delete;
     DeviceCtx &operator=(const DeviceCtx &) = delete;

@@ -4,8 +4,8 @@
 // frame order, their compressed and decoded bytes packed back to back), and
 // the (range, frame) overlaps -- the segments the gather kernel moves
 // (range_gather.hip).  No HIP and no reader state, so
-// tests/native/range_plan_shim.cpp unit-tests it on the CPU; reader.cpp's
-// vectored path uses exactly these.
+// tests/native/range_plan_shim.cpp unit-tests it on the CPU; reader_vec.cpp
+// uses exactly these.
 //
 // Replaces a caller's loop of zseek_pread calls over scattered ranges (the
 // reference has no vectored read: decompress.c:806-824 takes one range).

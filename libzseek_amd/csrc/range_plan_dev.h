@@ -62,7 +62,7 @@ namespace zsk {
 
 constexpr int64_t kPlanOverflow = -2;   // ZSK_PLAN_OVERFLOW
 constexpr int64_t kPlanSpan = -3;       // ZSK_PLAN_SPAN
-// the touched frames' compressed span the parse kernels can address (reader.cpp
+// the touched frames' compressed span the parse kernels can address (reader_vec.cpp
 // refuses a host-planned batch at the same bound): 2 GiB less the read slack
 constexpr uint64_t kPlanSpanLimit = 0x7FFFFF00ull;
 constexpr uint64_t kBadDst = ~0ull;     // RangeRow::full of a range with rtn == 0: destination outside the buffer

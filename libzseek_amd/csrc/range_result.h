@@ -3,7 +3,7 @@
 // host wait.  range_plan.h's range_results is the host form and the yardstick:
 // everything here gives exactly its answers.  No HIP runtime calls and no
 // reader state, so tests/native/range_result_shim.cpp drives it on the CPU;
-// range_result.hip's kernel and reader.cpp use exactly these.
+// range_result.hip's kernel and reader_vec.cpp use exactly these.
 //
 // The device gets a flat table of the call: one RangeRow per range and, per
 // touched frame t, t_doff[t] = d_off[P.frames[t]] -- all a result needs beside

@@ -39,85 +39,23 @@
 
 #include <algorithm>
 #include <chrono>
-#include <atomic>
-#include <deque>
 #include <functional>
-#include <memory>
-#include <mutex>
 #include <new>
-#include <shared_mutex>
 #include <thread>
 #include <utility>
-#include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/zseek_hip.h"
-#include "host.h"
 #include "lane_plan.h"
 #include "pool.h"
-#include "range_plan.h"
-#include "range_plan_dev.h"
-#include "range_result.h"
+#include "reader_internal.h"
 
 using namespace zsk;
 
 namespace {
 constexpr uint32_t kZstdMagic = 0xFD2FB528u;   // ref decompress.c:22
 constexpr uint32_t kLz4Magic = 0x184D2204u;    // ref decompress.c:23
-constexpr size_t kDefaultBatch = 64u << 20;    // decoded bytes per batch
 constexpr size_t kFirstBatch = 4u << 20;       // the first batch of a request (latency)
 constexpr size_t kLaneMin = 1u << 20;          // decoded bytes per lane, at least
 }   // namespace
-
-// A seekable file in device memory (zsk_reader_open_device): the frames are
-// decoded where they are.  The decode kernels get `base`, the image's start
-// rounded down to 256 bytes (the alignment of the hipMalloc'd staging they
-// otherwise read: zstd_decode.hip aligns its spans by c_off alone, so the base
-// itself must be 16-byte aligned), and descriptors whose c_off carry `bias`.
-struct DeviceImage {
-    const uint8_t *ptr = nullptr;    // the caller's image (not owned)
-    size_t size = 0;
-    int device = -1;
-    const uint8_t *base = nullptr;   // ptr rounded down to 256
-    uint64_t bias = 0;               // ptr - base
-    // the seek table, uploaded at open: c_off[n + 1], d_off[n + 1], then the
-    // n checksums when the file carries them
-    uint64_t *d_table = nullptr;
-    size_t table_bytes = 0;
-    const uint64_t *d_coff = nullptr, *d_doff = nullptr;
-    const uint32_t *d_ck = nullptr;
-    // the file's largest frame, decoded and compressed: what a device-planned
-    // read (preadv_indirect) sizes its staging and its parse scratch by
-    uint32_t max_dsize = 0, max_csize = 0;
-};
-
-struct zseek_reader {
-    zseek_read_file_t user_file;
-    DeviceImage *img = nullptr;   // NULL: the file comes through user_file
-    zseek_compression_type_t type;
-    // the reference's rwlock (decompress.c:38): shared for cache hits
-    // (:699-706), exclusive for misses, no-cache reads and GPU batches
-    // (:714-720); lru_lock orders the MRU promotion of concurrent hits (the
-    // reference promotes under its read lock, cache.c:125)
-    std::shared_mutex lock;
-    std::mutex lru_lock;
-    // zseek_reader_stats' changing fields, published under the exclusive
-    // lock after every change, read without the reader lock: a stats call
-    // never waits behind a multi-GiB GPU read (the reference takes its read
-    // lock, :850-875, and waits at most one frame decode)
-    std::atomic<size_t> snap_cache_memory{0}, snap_cached_frames{0}, snap_buffered{0};
-    std::mutex io_lock;   // one user pread callback at a time (lanes run in threads)
-    SeekTable st;
-    FrameCache *cache = nullptr;   // NULL when cache_size == 0 (ref :219-227)
-    std::mutex cursor_lock;        // zseek_read: cursor read, pread, advance as one step
-    size_t pos = 0;                // zseek_read cursor (ref :826-835)
-    size_t batch_bytes = kDefaultBatch;
-    int io_threads = 1;    // > 1: the caller allows concurrent pread callbacks
-    bool verify = false;   // check seek-table frame checksums (the reference never does)
-    std::vector<int> devices;                       // lane i decodes on devices[i]
-    std::vector<std::unique_ptr<DeviceCtx>> lanes;  // created at first use
-};
 
 // ---------------------------------------------------------------------------
 // default FILE* I/O (ref decompress.c:47-98): save position, seek, read,
@@ -381,84 +319,18 @@ bool zstd_partial_ok(int32_t st, uint64_t fail_at, uint64_t end_in_frame)
     return end_in_frame < fail_at;
 }
 
-// Error text for a failed frame, worded as the reference words the same
-// failure.  Cached reads decode the whole frame ("decompress frame: ...",
-// decompress.c:766-768); no-cache reads first decode-and-discard the
-// offset_in_frame prefix, then decode into the caller's buffer
-// (:635-660).  For a failure inside an LZ4 block liblz4 says ERROR_GENERIC
-// when the block was decoded straight into the destination (room >= max
-// block size) and ERROR_decompressionFailed when it went through its
-// temporary buffer; the room depends on which buffer the block landed in.
-void frame_error(zseek_reader *r, bool cached, int32_t st, uint32_t fail_at, size_t frame, size_t offset_in_frame,
-                 size_t count, char *errbuf)
+// Concurrent pread callbacks a batch may use: the reader's io_threads, at most
+// half the copy pool (the other half keeps the previous batch's host copies
+// moving: both run on the pool)
+int io_parts(const zseek_reader *r)
 {
-    const uint64_t dsize = r->st.dsize(frame);
-    const uint64_t at = fail_at;
-    const char *prefix;
-    uint64_t room;
-    if (cached) {
-        prefix = "decompress frame";
-        room = dsize - at;
-    } else if (offset_in_frame > 0 &&
-               (header_level(st) ? at <= offset_in_frame : at < offset_in_frame)) {
-        // the discard pass (decode-and-drop of the in-frame prefix) met it
-        prefix = "decompress discard data";
-        room = offset_in_frame - at;
-    } else {
-        prefix = "decompress user data";
-        uint64_t want = count < dsize - offset_in_frame ? count : dsize - offset_in_frame;
-        uint64_t used = at - offset_in_frame;
-        room = want > used ? want - used : 0;
-    }
-    if (r->type == ZSEEK_ZSTD) {
-        // libzstd: ZSTD_decompressDCtx (cached) or ZSTD_decompressStream
-        // (discard the in-frame prefix, then the caller's bytes,
-        // decompress.c:434-451); the discard pass meets a failure whose block
-        // starts at or before the prefix's end (a block is decoded as soon
-        // as the previous one is flushed)
-        if (!cached)
-            prefix = offset_in_frame > 0 && at <= offset_in_frame ? "decompress discard data"
-                                                                   : "decompress user data";
-        set_error(errbuf, "%s: %s", prefix, status_name(st));
-        return;
-    }
-    const char *name = status_name(st);
-    if (st & ST_BLOCK_FAIL_FLAG)
-        name = status_name(room >= status_max_block(st) ? ST_GENERIC : ST_DECOMPRESS_FAILED);
-    set_error(errbuf, "%s: %s", prefix, name);
+    const int half = copy_pool_threads() / 2;
+    return std::max(1, std::min(r->io_threads, half));
 }
 
 // ---------------------------------------------------------------------------
 // the batch pipeline of one lane (device)
 // ---------------------------------------------------------------------------
-struct CacheItem {
-    size_t frame;
-    uint8_t *data;   // malloc'd, owned until inserted
-    size_t len;
-};
-
-// One lane's share of a request: frames [fa, fb); bytes [offset, end) of the
-// decoded range go to buf at (x - offset).
-struct LaneJob {
-    zseek_reader *r = nullptr;
-    DeviceCtx *g = nullptr;
-    size_t fa = 0, fb = 0;
-    uint64_t offset = 0, end = 0;
-    uint8_t *buf = nullptr;
-    bool device_dst = false;
-    int dst_dev = -1;
-    void *call_data = nullptr;
-    size_t cache_cap = 0;   // keep the last cache_cap good frames' bytes
-    // results
-    bool io_failed = false;   // pread / HIP failure (err holds the text)
-    char err[ZSEEK_ERRBUF_SIZE] = {0};
-    size_t first_bad = SIZE_MAX;   // first failed frame, if any
-    int32_t status = ST_OK;
-    uint32_t fail_at = 0;
-    uint64_t good_end = 0;   // the lane's bytes before good_end are in buf
-    std::deque<CacheItem> cached;
-};
-
 void free_items(std::deque<CacheItem> &q)
 {
     for (CacheItem &c : q)
@@ -472,70 +344,6 @@ size_t batch_end(const SeekTable &st, size_t f, size_t fb, size_t limit)
     while (g < fb && st.d_off[g + 1] - st.d_off[f] <= limit)
         g++;
     return g;
-}
-
-// Concurrent pread callbacks a batch may use: the reader's io_threads, at most
-// half the copy pool (the other half keeps the previous batch's host copies
-// moving: both run on the pool)
-int io_parts(const zseek_reader *r)
-{
-    const int half = copy_pool_threads() / 2;
-    return std::max(1, std::min(r->io_threads, half));
-}
-
-// The batch's compressed span through the user's pread callback: one call
-// at a time (the reference's contract: it calls pread under the reader's
-// lock), or, where the caller allowed it (zsk_reader_set_io_threads), up to
-// io_threads concurrent calls on disjoint pieces of >= 4 MiB.
-bool read_span(LaneJob &J, uint8_t *dst, uint64_t len, uint64_t off)
-{
-    zseek_reader *r = J.r;
-    const uint64_t kPiece = 4u << 20;
-    const int parts = (int)std::min<uint64_t>((uint64_t)io_parts(r), len / kPiece);
-    if (parts <= 1) {
-        std::lock_guard<std::mutex> io(r->io_lock);
-        ssize_t got = r->user_file.pread(dst, len, off, r->user_file.user_data, J.call_data);
-        if (got != (ssize_t)len) {
-            // ref decompress.c:735-741
-            set_error(J.err, got >= 0 ? "unexpected EOF" : "read file failed");
-            return false;
-        }
-        return true;
-    }
-    std::vector<ssize_t> got(parts, 0);
-    CopyTicket t;
-    const uint64_t per = (len / parts + 4095) & ~4095ull;
-    for (int i = 0; i < parts; i++) {
-        const uint64_t a = std::min<uint64_t>(len, per * i), b = std::min<uint64_t>(len, per * (i + 1));
-        pool_run([&, i, a, b] {
-            got[i] = b > a ? r->user_file.pread(dst + a, b - a, off + a, r->user_file.user_data, J.call_data)
-                           : 0;
-            if (got[i] == (ssize_t)(b - a))
-                got[i] = 0;   // complete
-            else if (got[i] >= 0)
-                got[i] = 1;   // short: EOF
-        }, &t);
-    }
-    pool_wait(&t);
-    for (int i = 0; i < parts; i++)
-        if (got[i] != 0) {
-            set_error(J.err, got[i] > 0 ? "unexpected EOF" : "read file failed");
-            return false;
-        }
-    return true;
-}
-
-// read_span's stand-in for a file in device memory, whose frames are decoded
-// where they are: nothing is read, but a compressed span that the seek table
-// puts past the end of the image (a corrupt or hostile table: open only sums
-// its entries) fails exactly where the pread of a host copy comes back short,
-// before any kernel gets a descriptor that points outside the image.
-bool image_span(LaneJob &J, const DeviceImage *img, uint64_t len, uint64_t off)
-{
-    if (off <= img->size && len <= img->size - off)
-        return true;
-    set_error(J.err, "unexpected EOF");
-    return false;
 }
 
 #ifdef ZSK_TUNING
@@ -609,13 +417,12 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     const DeviceImage *const img = r->img;
     // the descriptors ride behind the compressed span (past its 256-byte
     // read slack) in the same pinned buffer and the same upload
-    const uint64_t doff = img ? 0 : (csz + 256 + 255) & ~255ull;
     // (zstd, a request's few frames: the host plan rides behind them too;
     // not for a device image, whose bytes the host never sees: the device
     // plan and its synchronization)
     const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
-    const uint64_t poff = doff + n * sizeof(FrameDesc), up = poff + (zplan ? 16 * (n + 1) : 0);
-    if (!s.reserve(up, dsz, br.h_len, n, ck, J.err)) {
+    const BatchLayout L = contiguous_layout(csz, n, img != nullptr, zplan);
+    if (!s.reserve(L.up, dsz, br.h_len, n, ck, J.err)) {
         J.io_failed = true;
         return false;
     }
@@ -625,8 +432,8 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
     }
     HT_ADD(0, ht0)
     HT_T(ht1)
-    FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + doff);
-    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + doff);
+    FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + L.doff);
+    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + L.doff);
     // what the kernels read the frames from: the slot's staging, or the image
     // in place (its 256-aligned base; the descriptors' c_off carry the rest)
     const uint8_t *const comp = img ? img->base : s.d_comp;
@@ -641,15 +448,10 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
         d.d_size = (uint32_t)st.dsize(f0 + i);
         max_dsize = std::max(max_dsize, d.d_size);
     }
-    s.f0 = f0;
-    s.f1 = f1;
-    // per-frame status then fail_at, back to back (one download for both)
-    uint32_t *d_fail = reinterpret_cast<uint32_t *>(s.d_status + n);
-    s.h_from = br.h_from;
-    s.h_len = br.h_len;
+    s.begin_batch(f0, f1, br.h_from, br.h_len);
     ZstdHostPlan zp{};
     if (zplan)
-        zstd_host_plan(h_desc, s.h_comp, (uint32_t)n, reinterpret_cast<uint64_t *>(s.h_comp + poff), &zp);
+        zstd_host_plan(h_desc, s.h_comp, (uint32_t)n, reinterpret_cast<uint64_t *>(s.h_comp + L.poff), &zp);
     hipError_t e = hipSuccess;
     // (a small upload as a kernel on the stream: no DMA hand-off before the
     // decode's first kernel, host_io.hip; env ZSEEK_HOST_DMA=1: always DMA,
@@ -661,81 +463,48 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
         const char *v = getenv("ZSEEK_DONE_FLAG");
         return v && !strcmp(v, "0");
     }();
-    s.flagged = false;
-    // (the LZ4 two-phase decoder's plan kernel initializes both itself, the
-    // zstd sequence kernel writes both for every frame)
-    const bool lz4_split = r->type == ZSEEK_LZ4 && lz4_pick_engine((uint32_t)n) != ENGINE_WAVE;
     if (img) {
         if (launch_image_desc(img->d_coff, img->d_doff, f0, (uint32_t)n, img->bias,
                               reinterpret_cast<FrameDesc *>(s.d_comp), s.stream) != 0)
             e = hipErrorLaunchFailure;
     } else if (host_dma)
-        e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, s.stream);
-    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, s.stream) != 0)
+        e = hipMemcpyAsync(s.d_comp, s.h_comp, L.up, hipMemcpyHostToDevice, s.stream);
+    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, L.up, s.stream) != 0)
         e = hipErrorLaunchFailure;
-    const bool preset = r->type == ZSEEK_LZ4 && !lz4_split;
-    if (e == hipSuccess && preset)
-        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, n, s.stream);
-    if (e == hipSuccess && preset)
-        e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, n, s.stream);
-    // (zstd: a request's few frames are planned on the host from the pinned
-    // span -- no plan launch, no synchronization between plan and decode)
-    if (e == hipSuccess && r->type == ZSEEK_ZSTD &&
-        (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
-                                            (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, s.stream, d_fail,
-                                            stop_last)
-                            : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs,
-                                                 s.stream, d_fail, stop_last)) != 0)
-        e = hipErrorLaunchFailure;
-    if (e == hipSuccess && r->type == ZSEEK_LZ4) {
-        if (lz4_pick_engine((uint32_t)n) == ENGINE_WAVE) {
-            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream) != 0)
-                e = hipErrorLaunchFailure;
-        } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
-                                         s.stream) != 0) {
-            e = hipErrorOutOfMemory;
-        } else {
-            // a lone frame with a host destination (or none): its execute
-            // writes the status words, the bytes and the completion word
-            // itself when it takes the one-frame route (no download kernel)
-            HostPost post;
-            const bool want_post = n == 1 && !host_dma && !no_flag && !ck && br.route != COPY_DEVICE &&
-                                   br.route != COPY_PEER && s.h_status_dev &&
-                                   (!s.h_len || (s.h_out_dev && !(reinterpret_cast<uintptr_t>(s.h_out_dev) & 15)));
-            if (want_post) {
-                if (s.h_len)
-                    pool_wait(&s.copies);   // (the execute writes h_out)
-                s.h_flag = reinterpret_cast<volatile uint32_t *>(s.h_status + 2 * n);
-                *s.h_flag = 0;
-                s.seq = s.seq + 1 ? s.seq + 1 : 1;
-                post.h_status = reinterpret_cast<uint32_t *>(s.h_status_dev);
-                post.h_out = static_cast<uint8_t *>(s.h_out_dev);
-                post.h_from = (uint32_t)s.h_from;
-                post.h_len = (uint32_t)s.h_len;
-                post.h_flag = reinterpret_cast<uint32_t *>(s.h_status_dev) + 2 * n;
-                post.seq = s.seq;
-            }
-            bool posted = false;
-            if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, s.stream, &s.split,
-                                 ROUTE_AUTO, 15, 0, stop_last, max_dsize, want_post ? &post : nullptr,
-                                 &posted, true) != 0)
-                e = hipErrorLaunchFailure;
-            s.flagged = posted;
-        }
+    DecodeBatch dec{r->type, s.stream, d_desc, (uint32_t)n, comp, max_dsize, stop_last};
+    dec.zplan = zplan ? &zp : nullptr;
+    dec.d_plan = reinterpret_cast<const uint64_t *>(s.d_comp + L.poff);
+    dec.h_desc = h_desc;
+    // a lone frame with a host destination (or none): its execute writes the
+    // status words, the bytes and the completion word itself when it takes the
+    // one-frame route (no download kernel)
+    HostPost post;
+    const bool lz4_split = r->type == ZSEEK_LZ4 && !lz4_wave_batch(r->type, n);
+    if (lz4_split && n == 1 && !host_dma && !no_flag && !ck && br.route != COPY_DEVICE &&
+        br.route != COPY_PEER && s.h_status_dev &&
+        (!s.h_len || (s.h_out_dev && !(reinterpret_cast<uintptr_t>(s.h_out_dev) & 15)))) {
+        if (s.h_len)
+            pool_wait(&s.copies);   // (the execute writes h_out)
+        s.h_flag = reinterpret_cast<volatile uint32_t *>(s.h_status + 2 * n);
+        *s.h_flag = 0;
+        s.seq = s.seq + 1 ? s.seq + 1 : 1;
+        post.h_status = reinterpret_cast<uint32_t *>(s.h_status_dev);
+        post.h_out = static_cast<uint8_t *>(s.h_out_dev);
+        post.h_from = (uint32_t)s.h_from;
+        post.h_len = (uint32_t)s.h_len;
+        post.h_flag = reinterpret_cast<uint32_t *>(s.h_status_dev) + 2 * n;
+        post.seq = s.seq;
+        dec.post = &post;
     }
-    // seek-table checksums (descriptor bit 7) when asked for: XXH64 low 32
-    // bits of every decoded frame, on the GPU (frame_check.hip)
-    if (e == hipSuccess && ck) {
+    dec.posted = &s.flagged;
+    if (ck) {
         // (a device image: the batch's n words of the resident table, at f0)
-        const uint32_t *d_want = img ? img->d_ck + f0 : s.d_ck;
-        if (!img) {
+        dec.d_want = img ? img->d_ck + f0 : s.d_ck;
+        if (!img)
             memcpy(s.h_ck, st.checksum.data() + f0, n * sizeof(uint32_t));
-            e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream);
-        }
-        if (e == hipSuccess &&
-            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, d_want, s.d_status, s.stream) != 0)
-            e = hipErrorLaunchFailure;
     }
+    if (e == hipSuccess)
+        e = decode_batch(s, dec);
     // decoded bytes out: straight into a device destination (a peer copy from
     // another lane's device), or into the slot's pinned bounce once the host
     // copies of its previous batch are done; the status words and the bounce
@@ -783,10 +552,7 @@ bool submit(LaneJob &J, Slot &s, size_t f0, size_t f1)
         (void)hipStreamSynchronize(s.stream);
         return false;
     }
-    g.batches++;
-    g.frames_decoded += n;
-    g.bytes_decoded += dsz;
-    g.bytes_uploaded += img ? 0 : csz;
+    g.count_batch(n, dsz, img ? 0 : csz);
     HT_ADD(1, ht1)
 #ifdef ZSK_TUNING
     t_queued = ht_now();
@@ -905,65 +671,21 @@ void run_lane(LaneJob &J)
     DeviceCtx &g = *J.g;
     (void)hipSetDevice(g.device);
     J.good_end = std::max<uint64_t>(J.offset, J.r->st.d_off[J.fa]);
-    std::deque<int> inflight;
     size_t f = J.fa;
-    int next = 0;
-    bool stop = false;
     size_t limit = std::min(kFirstBatch, J.r->batch_bytes);
-    for (;;) {
-        if (!stop && f < J.fb && (int)inflight.size() < kSlots) {
+    run_in_flight(
+        g,
+        [&](Slot &s, size_t) {
+            if (f >= J.fb)
+                return kNoneLeft;
             const size_t gend = batch_end(J.r->st, f, J.fb, limit);
             limit = J.r->batch_bytes;
-            if (!submit(J, g.slot[next], f, gend)) {
-                stop = true;
-                continue;
-            }
-            inflight.push_back(next);
-            next = (next + 1) % kSlots;
+            if (!submit(J, s, f, gend))
+                return kQueueFailed;
             f = gend;
-            continue;
-        }
-        if (inflight.empty())
-            break;
-        Slot &s = g.slot[inflight.front()];
-        inflight.pop_front();
-        if (stop) {   // a failure before this batch: drain it, keep nothing
-            (void)hipEventSynchronize(s.done);
-            continue;
-        }
-        if (!finish(J, s))
-            stop = true;
-    }
-    for (Slot &s : g.slot)
-        pool_wait(&s.copies);
-}
-
-bool ensure_lanes(zseek_reader *r, char *errbuf)
-{
-    if (r->devices.empty())
-        r->devices = default_devices();
-    if (r->devices.empty()) {
-        set_error(errbuf, "no HIP device available");
-        return false;
-    }
-    while (r->lanes.size() < r->devices.size())
-        r->lanes.emplace_back(new DeviceCtx());
-    for (size_t i = 0; i < r->devices.size(); i++)
-        if (!r->lanes[i]->init(r->devices[i], errbuf))
-            return false;
-    return true;
-}
-
-// The reader's stats fields that change (cache, staging) -> the lock-free
-// snapshot zseek_reader_stats reads; called under the exclusive lock.
-void publish_stats(zseek_reader *r)
-{
-    r->snap_cache_memory.store(r->cache ? r->cache->memory_usage() : 0, std::memory_order_relaxed);
-    r->snap_cached_frames.store(r->cache ? r->cache->entries() : 0, std::memory_order_relaxed);
-    size_t buffered = 0;
-    for (auto &l : r->lanes)
-        buffered += l->host_bytes();
-    r->snap_buffered.store(buffered, std::memory_order_relaxed);
+            return kQueued;
+        },
+        [&](Slot &s, size_t) { return finish(J, s); });
 }
 
 // bytes [rel, rel + count) of a cached frame (len bytes) -> the caller's
@@ -1011,10 +733,7 @@ ssize_t pread_frames(zseek_reader *r, void *buf, size_t count, size_t offset, vo
             return copy_slice(buf, data, len, offset - st.d_off[f_first], count, device_dst, errbuf);
     }
     std::unique_lock<std::shared_mutex> guard(r->lock);
-    struct Publish {   // the stats snapshot once this request is done
-        zseek_reader *r;
-        ~Publish() { publish_stats(r); }
-    } publish{r};
+    PublishStats publish{r};
     // single-frame request with a cache: the reference's cached path
     // (decompress.c:699-796), GPU-decoded on a miss (one batch of one frame,
     // one synchronisation)
@@ -1141,712 +860,178 @@ ssize_t pread_frames(zseek_reader *r, void *buf, size_t count, size_t offset, vo
     return done;
 }
 
-// ---------------------------------------------------------------------------
-// vectored read (zsk_preadv, zsk_preadv_device): range_plan.h's batches
-// through the first lane's slots.  A batch holds only the frames its ranges
-// touch, read run by run and packed back to back; the decode is submit()'s,
-// every frame whole (stop_last off); the bytes leave through the gather
-// kernel (range_gather.hip), segment by segment.
-// ---------------------------------------------------------------------------
-struct VecJob {
-    LaneJob J;   // r, g, call_data, err, io_failed: read_span's context
-    const RangePlan *P = nullptr;
-    uint8_t *buf = nullptr;
-    bool device_dst = false;
-    std::vector<int32_t> status;     // per touched frame (P->frames)
-    std::vector<uint32_t> fail_at;
-    // zsk_preadv_device_async: the batch's commands go on the caller's stream
-    // `q` (NULL: the null stream) and nobody waits for them; its statuses are
-    // appended on that stream to d_call_status (per touched frame, the call's
-    // CallTable) instead of downloaded, and there is no finish_gather
-    bool async = false;
-    hipStream_t q = nullptr;
-    int32_t *d_call_status = nullptr;
-};
+}   // namespace
 
-// Read, upload, decode and gather batch bi on slot s.  Asynchronous mode
-// (V.async): everything is queued on the caller's stream, directly -- the
-// slot's own stream is not used, so "stream-ordered" needs no event bridge --
-// and the slot is left `pending` behind its `done` event for its next user
-// to drain.
-bool submit_gather(VecJob &V, Slot &s, size_t bi)
+// ---- shared with reader_vec.cpp (reader_internal.h) ------------------------
+
+// Error text for a failed frame, worded as the reference words the same
+// failure.  Cached reads decode the whole frame ("decompress frame: ...",
+// decompress.c:766-768); no-cache reads first decode-and-discard the
+// offset_in_frame prefix, then decode into the caller's buffer
+// (:635-660).  For a failure inside an LZ4 block liblz4 says ERROR_GENERIC
+// when the block was decoded straight into the destination (room >= max
+// block size) and ERROR_decompressionFailed when it went through its
+// temporary buffer; the room depends on which buffer the block landed in.
+void zsk::frame_error(zseek_reader *r, bool cached, int32_t st, uint32_t fail_at, size_t frame,
+                      size_t offset_in_frame, size_t count, char *errbuf)
 {
-    zseek_reader *r = V.J.r;
-    DeviceCtx &g = *V.J.g;
-    const SeekTable &st = r->st;
-    const RangePlan &P = *V.P;
-    const PlanBatch &b = P.batches[bi];
-    const size_t n = b.t1 - b.t0, nseg = b.s1 - b.s0;
-    uint64_t csz = 0;
-    for (size_t t = b.t0; t < b.t1; t++)
-        csz += st.csize(P.frames[t]);
-    const uint64_t dsz = b.d_bytes;
-    const bool ck = r->verify && st.checksum_flag;
-    // a host destination: the segments compacted (in segment order, P.cum)
-    // into the slot's pinned bounce -- by the gather itself through the
-    // bounce's device mapping when the batch is small (download_small's
-    // bound), else compacted behind the decoded bytes in d_out and brought
-    // down by one DMA
-    const uint64_t h_len = V.device_dst ? 0 : b.out_bytes;
-    const uint64_t pack_at = (dsz + 255) & ~255ull;
-    (void)hipSetDevice(g.device);
-    // the slot's previous asynchronous batch must have finished before the
-    // host rewrites its pinned staging below (a host wait, the one a fourth
-    // batch in flight costs)
-    s.drain();
-    hipStream_t const q = V.async ? V.q : s.stream;
-    if (h_len > s.h_out_cap)
-        pool_wait(&s.copies);
-    // a file in device memory: nothing is read or packed -- the touched frames
-    // are decoded where they are, from host-built descriptors (the host has
-    // the whole table, and a vectored batch's d_off is a scan over its sparse
-    // frame list; they ride in the small upload that carries the segments
-    // anyway, so a device-side builder would save no transfer)
-    const DeviceImage *const img = r->img;
-    // behind the packed compressed bytes and their 256-byte read slack: the
-    // descriptors, the zstd host plan, the segments, their prefix sum
-    const uint64_t doff = img ? 0 : (csz + 256 + 255) & ~255ull;
-    const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
-    const uint64_t poff = doff + n * sizeof(FrameDesc), goff = poff + (zplan ? 16 * (n + 1) : 0);
-    const uint64_t coff = goff + nseg * sizeof(GatherSeg), up = coff + (nseg + 1) * sizeof(uint64_t);
-    if (!s.reserve(up, pack_at + h_len, h_len, n, ck, V.J.err)) {
-        V.J.io_failed = true;
-        return false;
+    const uint64_t dsize = r->st.dsize(frame);
+    const uint64_t at = fail_at;
+    const char *prefix;
+    uint64_t room;
+    if (cached) {
+        prefix = "decompress frame";
+        room = dsize - at;
+    } else if (offset_in_frame > 0 &&
+               (header_level(st) ? at <= offset_in_frame : at < offset_in_frame)) {
+        // the discard pass (decode-and-drop of the in-frame prefix) met it
+        prefix = "decompress discard data";
+        room = offset_in_frame - at;
+    } else {
+        prefix = "decompress user data";
+        uint64_t want = count < dsize - offset_in_frame ? count : dsize - offset_in_frame;
+        uint64_t used = at - offset_in_frame;
+        room = want > used ? want - used : 0;
     }
-    uint64_t c_at = 0;
-    for (size_t ri = b.r0; ri < b.r1; ri++) {   // one pread per run of adjacent frames (an image: its bounds)
-        const uint64_t c0 = st.c_off[P.runs[ri].f0], len = st.c_off[P.runs[ri].f1] - c0;
-        if (len && !(img ? image_span(V.J, img, len, c0) : read_span(V.J, s.h_comp + c_at, len, c0))) {
-            V.J.io_failed = true;
+    if (r->type == ZSEEK_ZSTD) {
+        // libzstd: ZSTD_decompressDCtx (cached) or ZSTD_decompressStream
+        // (discard the in-frame prefix, then the caller's bytes,
+        // decompress.c:434-451); the discard pass meets a failure whose block
+        // starts at or before the prefix's end (a block is decoded as soon
+        // as the previous one is flushed)
+        if (!cached)
+            prefix = offset_in_frame > 0 && at <= offset_in_frame ? "decompress discard data"
+                                                                   : "decompress user data";
+        set_error(errbuf, "%s: %s", prefix, status_name(st));
+        return;
+    }
+    const char *name = status_name(st);
+    if (st & ST_BLOCK_FAIL_FLAG)
+        name = status_name(room >= status_max_block(st) ? ST_GENERIC : ST_DECOMPRESS_FAILED);
+    set_error(errbuf, "%s: %s", prefix, name);
+}
+
+// The batch's compressed span through the user's pread callback: one call
+// at a time (the reference's contract: it calls pread under the reader's
+// lock), or, where the caller allowed it (zsk_reader_set_io_threads), up to
+// io_threads concurrent calls on disjoint pieces of >= 4 MiB.
+bool zsk::read_span(LaneJob &J, uint8_t *dst, uint64_t len, uint64_t off)
+{
+    zseek_reader *r = J.r;
+    const uint64_t kPiece = 4u << 20;
+    const int parts = (int)std::min<uint64_t>((uint64_t)io_parts(r), len / kPiece);
+    if (parts <= 1) {
+        std::lock_guard<std::mutex> io(r->io_lock);
+        ssize_t got = r->user_file.pread(dst, len, off, r->user_file.user_data, J.call_data);
+        if (got != (ssize_t)len) {
+            // ref decompress.c:735-741
+            set_error(J.err, got >= 0 ? "unexpected EOF" : "read file failed");
             return false;
         }
-        c_at += len;
-    }
-    // (the parse kernels address a wave's frames through one 32-bit buffer
-    // resource: the planner's span cut keeps a batch far below it unless
-    // batch_bytes was set to 512 MiB or more)
-    if (img && n && st.c_off[P.frames[b.t1 - 1] + 1] - st.c_off[P.frames[b.t0]] >= 0x7FFFFF00ull) {
-        set_error(V.J.err, "vectored read: a batch spans 2 GiB of the device image");
-        V.J.io_failed = true;
-        return false;
-    }
-    FrameDesc *const h_desc = reinterpret_cast<FrameDesc *>(s.h_comp + doff);
-    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(s.d_comp + doff);
-    const uint8_t *const comp = img ? img->base : s.d_comp;
-    uint32_t max_dsize = 0;
-    uint64_t c = 0, d = 0;
-    for (size_t i = 0; i < n; i++) {
-        const size_t f = P.frames[b.t0 + i];
-        FrameDesc &fd = h_desc[i];
-        fd.c_off = img ? st.c_off[f] + img->bias : c;
-        fd.d_off = d;
-        fd.c_size = (uint32_t)st.csize(f);
-        fd.d_size = (uint32_t)st.dsize(f);
-        c += fd.c_size;
-        d += fd.d_size;
-        max_dsize = std::max(max_dsize, fd.d_size);
-    }
-    GatherSeg *const h_seg = reinterpret_cast<GatherSeg *>(s.h_comp + goff);
-    const uint64_t *const cum = P.cum.data() + b.s0 + bi;
-    for (size_t i = 0; i < nseg; i++) {
-        const PlanSeg &ps = P.segs[b.s0 + i];
-        h_seg[i] = {ps.src_off, V.device_dst ? ps.dst_off : cum[i], ps.len, ps.frame};
-    }
-    memcpy(s.h_comp + coff, cum, (nseg + 1) * sizeof(uint64_t));
-    s.f0 = s.f1 = 0;
-    s.h_from = 0;
-    s.h_len = h_len;
-    s.flagged = false;
-    uint32_t *d_fail = reinterpret_cast<uint32_t *>(s.d_status + n);
-    ZstdHostPlan zp{};
-    if (zplan)
-        zstd_host_plan(h_desc, s.h_comp, (uint32_t)n, reinterpret_cast<uint64_t *>(s.h_comp + poff), &zp);
-    static const bool host_dma = getenv("ZSEEK_HOST_DMA") != nullptr;
-    const uint32_t stop_last = 0xFFFFFFFFu;
-    const bool wave = r->type == ZSEEK_LZ4 && lz4_pick_engine((uint32_t)n) == ENGINE_WAVE;
-    hipError_t e = hipSuccess;
-    if (host_dma)
-        e = hipMemcpyAsync(s.d_comp, s.h_comp, up, hipMemcpyHostToDevice, q);
-    else if (upload_small(s.d_comp, s.h_comp, s.h_comp_dev, up, q) != 0)
-        e = hipErrorLaunchFailure;
-    if (e == hipSuccess && wave)
-        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, n, q);
-    if (e == hipSuccess && wave)
-        e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, n, q);
-    if (e == hipSuccess && r->type == ZSEEK_ZSTD &&
-        (zplan ? zstd_decode_frames_planned(zp, reinterpret_cast<const uint64_t *>(s.d_comp + poff), d_desc,
-                                            (uint32_t)n, s.d_comp, s.d_out, s.d_status, &s.zs, q, d_fail,
-                                            stop_last)
-               : zstd_decode_frames(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, &s.zs, q, d_fail,
-                                    stop_last)) != 0)
-        e = hipErrorLaunchFailure;
-    if (e == hipSuccess && r->type == ZSEEK_LZ4) {
-        if (wave) {
-            if (launch_lz4_wave(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, q) != 0)
-                e = hipErrorLaunchFailure;
-        } else if (split_scratch_reserve(&s.split, (uint32_t)n, split_items_needed(h_desc, (uint32_t)n),
-                                         q) != 0) {
-            e = hipErrorOutOfMemory;
-        } else if (launch_lz4_split(d_desc, (uint32_t)n, comp, s.d_out, s.d_status, d_fail, q, &s.split,
-                                    ROUTE_AUTO, 15, 0, stop_last, max_dsize, nullptr, nullptr, true) != 0) {
-            e = hipErrorLaunchFailure;
-        }
-    }
-    if (e == hipSuccess && ck) {
-        for (size_t i = 0; i < n; i++)
-            s.h_ck[i] = st.checksum[P.frames[b.t0 + i]];
-        e = hipMemcpyAsync(s.d_ck, s.h_ck, n * sizeof(uint32_t), hipMemcpyHostToDevice, q);
-        if (e == hipSuccess &&
-            launch_frame_checksums(d_desc, (uint32_t)n, s.d_out, s.d_ck, s.d_status, q) != 0)
-            e = hipErrorLaunchFailure;
-    }
-    // the segments of the frames that decoded: into the caller's device
-    // buffer, or compacted for the host (the slot's previous batch must have
-    // left the bounce first)
-    if (e == hipSuccess && h_len)
-        pool_wait(&s.copies);
-    if (e == hipSuccess && b.out_bytes) {
-        const bool mapped = h_len && !host_dma && h_len <= kDownloadSmallMax && s.h_out_dev;
-        uint8_t *const dst = V.device_dst ? V.buf : mapped ? static_cast<uint8_t *>(s.h_out_dev) : s.d_out + pack_at;
-        if (launch_range_gather(reinterpret_cast<const GatherSeg *>(s.d_comp + goff),
-                                reinterpret_cast<const uint64_t *>(s.d_comp + coff), (uint32_t)nseg, b.out_bytes,
-                                s.d_out, dst, s.d_status, q) != 0)
-            e = hipErrorLaunchFailure;
-        if (e == hipSuccess && h_len && !mapped)
-            e = hipMemcpyAsync(s.h_out, s.d_out + pack_at, h_len, hipMemcpyDeviceToHost, q);
-    }
-    // the statuses: downloaded for finish_gather, or (asynchronous) kept on the
-    // device, appended to the call's, which outlive the slot's reuse by a later
-    // batch (a range can span batches)
-    if (e == hipSuccess && V.async)
-        e = hipMemcpyAsync(V.d_call_status + b.t0, s.d_status, n * sizeof(int32_t), hipMemcpyDeviceToDevice, q);
-    else if (e == hipSuccess &&
-             download_small(reinterpret_cast<uint32_t *>(s.h_status), host_dma ? nullptr : s.h_status_dev,
-                            reinterpret_cast<const uint32_t *>(s.d_status), (uint32_t)(2 * n), nullptr, nullptr,
-                            s.d_out, 0, q) != 0)
-        e = hipErrorLaunchFailure;
-    // (asynchronous: whatever was queued, a failed batch's part included, is
-    // behind `done`; the slot's next user waits for it, this call does not)
-    if (e == hipSuccess || V.async) {
-        const hipError_t er = hipEventRecord(s.done, q);
-        s.pending = V.async && er == hipSuccess;
-        if (e == hipSuccess)
-            e = er;
-    }
-    if (e != hipSuccess) {
-        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
-        V.J.io_failed = true;
-        if (!s.pending)
-            (void)hipStreamSynchronize(q);
-        return false;
-    }
-    g.batches++;
-    g.frames_decoded += n;
-    g.bytes_decoded += dsz;
-    g.bytes_uploaded += img ? 0 : csz;
-    return true;
-}
-
-// Wait for batch bi on slot s: keep its frames' statuses and, for a host
-// destination, scatter the bounce into the caller's buffer on the pool (the
-// segments of failed frames are left out: the gather skipped them).
-bool finish_gather(VecJob &V, Slot &s, size_t bi)
-{
-    const RangePlan &P = *V.P;
-    const PlanBatch &b = P.batches[bi];
-    const size_t n = b.t1 - b.t0;
-    const hipError_t e = hipEventSynchronize(s.done);
-    if (e != hipSuccess) {
-        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
-        V.J.io_failed = true;
-        return false;
-    }
-    for (size_t i = 0; i < n; i++) {
-        V.status[b.t0 + i] = s.h_status[i];
-        V.fail_at[b.t0 + i] = reinterpret_cast<const uint32_t *>(s.h_status + n)[i];
-    }
-    if (V.device_dst || !b.out_bytes)
         return true;
-    // pieces of >= 256 KiB, about one per pool thread
-    const uint64_t piece = std::max<uint64_t>(256u << 10, b.out_bytes / (uint64_t)copy_pool_threads() + 1);
-    const uint64_t *const cum = P.cum.data() + b.s0 + bi;
-    const PlanSeg *const segs = P.segs.data() + b.s0;
-    const int32_t *const status = V.status.data() + b.t0;
-    const uint8_t *const bounce = s.h_out;
-    uint8_t *const buf = V.buf;
-    const size_t nseg = b.s1 - b.s0;
-    for (size_t i = 0; i < nseg;) {
-        size_t j = i + 1;
-        while (j < nseg && cum[j] - cum[i] < piece)
-            j++;
-        pool_run([=] {
-            for (size_t k = i; k < j; k++)
-                if (status[segs[k].frame] == ST_OK)
-                    memcpy(buf + segs[k].dst_off, bounce + cum[k], segs[k].len);
-        }, &s.copies);
-        i = j;
     }
+    std::vector<ssize_t> got(parts, 0);
+    CopyTicket t;
+    const uint64_t per = (len / parts + 4095) & ~4095ull;
+    for (int i = 0; i < parts; i++) {
+        const uint64_t a = std::min<uint64_t>(len, per * i), b = std::min<uint64_t>(len, per * (i + 1));
+        pool_run([&, i, a, b] {
+            got[i] = b > a ? r->user_file.pread(dst + a, b - a, off + a, r->user_file.user_data, J.call_data)
+                           : 0;
+            if (got[i] == (ssize_t)(b - a))
+                got[i] = 0;   // complete
+            else if (got[i] >= 0)
+                got[i] = 1;   // short: EOF
+        }, &t);
+    }
+    pool_wait(&t);
+    for (int i = 0; i < parts; i++)
+        if (got[i] != 0) {
+            set_error(J.err, got[i] > 0 ? "unexpected EOF" : "read file failed");
+            return false;
+        }
     return true;
 }
 
-ssize_t preadv_frames(zseek_reader *r, void *buf, zsk_range_t *ranges, size_t nranges, void *call_data, char *errbuf,
-                      bool device_dst)
+// read_span's stand-in for a file in device memory, whose frames are decoded
+// where they are: nothing is read, but a compressed span that the seek table
+// puts past the end of the image (a corrupt or hostile table: open only sums
+// its entries) fails exactly where the pread of a host copy comes back short,
+// before any kernel gets a descriptor that points outside the image.
+bool zsk::image_span(LaneJob &J, const DeviceImage *img, uint64_t len, uint64_t off)
 {
-    static_assert(sizeof(zsk_segment_t) == sizeof(GatherSeg), "segment ABI");
-    for (size_t i = 0; ranges && i < nranges; i++)
-        ranges[i].result = -1;
-    if (!r) {
-        set_error(errbuf, "invalid reader");
-        return -1;
-    }
-    if (nranges == 0)
-        return 0;
-    if (!ranges) {
-        set_error(errbuf, "invalid ranges");
-        return -1;
-    }
-    const SeekTable &st = r->st;
-    std::vector<RangeReq> req(nranges);
-    for (size_t i = 0; i < nranges; i++)
-        req[i] = {ranges[i].offset, ranges[i].count, ranges[i].dst_off};
-    DeviceGuard keep_device;
-    std::unique_lock<std::shared_mutex> guard(r->lock);
-    struct Publish {
-        zseek_reader *r;
-        ~Publish() { publish_stats(r); }
-    } publish{r};
-    const size_t nframes = st.frames();
-    const uint64_t zero = 0;
-    const uint64_t *const d_off = nframes ? st.d_off.data() : &zero;
-    // a device image's frames are decoded where they lie: the LZ4 plan lays
-    // item slots out by compressed distance and the parse kernels address a
-    // wave's frames through one 32-bit resource, so a batch of sparse frames is
-    // also cut by the compressed span it covers (4 x batch_bytes: 256 MiB by default)
-    const RangePlan P = r->img && nframes ? plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes,
-                                                        st.c_off.data(), (uint64_t)std::min<size_t>(r->batch_bytes, SIZE_MAX / 4) * 4)
-                                          : plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
-    VecJob V;
-    V.P = &P;
-    V.buf = static_cast<uint8_t *>(buf);
-    V.device_dst = device_dst;
-    V.status.assign(P.frames.size(), ST_NOT_RUN);
-    V.fail_at.assign(P.frames.size(), 0);
-    if (!P.batches.empty()) {
-        if (!buf && !P.segs.empty()) {
-            set_error(errbuf, "invalid buffer");
-            return -1;
-        }
-        for (const PlanBatch &b : P.batches)
-            if (b.s1 - b.s0 >= 0xFFFFFFFFull || b.t1 - b.t0 >= 0x7FFFFFFFull) {
-                set_error(errbuf, "too many ranges");
-                return -1;
-            }
-        if (!ensure_lanes(r, errbuf))
-            return -1;
-        DeviceCtx &g = *r->lanes[0];
-        V.J.r = r;
-        V.J.g = &g;
-        V.J.call_data = call_data;
-        (void)hipSetDevice(g.device);
-        // up to kSlots batches in flight, finished in order (as run_lane)
-        std::deque<std::pair<int, size_t>> inflight;
-        size_t bi = 0;
-        int next = 0;
-        bool stop = false;
-        for (;;) {
-            if (!stop && bi < P.batches.size() && (int)inflight.size() < kSlots) {
-                if (!submit_gather(V, g.slot[next], bi)) {
-                    stop = true;
-                    continue;
-                }
-                inflight.push_back({next, bi});
-                next = (next + 1) % kSlots;
-                bi++;
-                continue;
-            }
-            if (inflight.empty())
-                break;
-            Slot &s = g.slot[inflight.front().first];
-            const size_t done = inflight.front().second;
-            inflight.pop_front();
-            if (stop) {
-                (void)hipEventSynchronize(s.done);
-                continue;
-            }
-            if (!finish_gather(V, s, done))
-                stop = true;
-        }
-        for (Slot &s : g.slot)
-            pool_wait(&s.copies);
-        if (V.J.io_failed) {
-            set_error(errbuf, "%s", V.J.err);
-            return -1;
-        }
-    }
-    std::vector<int64_t> result(nranges);
-    std::vector<size_t> bad(nranges);
-    const size_t ok = range_results(P, req.data(), nranges, d_off, nframes, V.status.data(), result.data(), bad.data());
-    bool reported = false;
-    for (size_t i = 0; i < nranges; i++) {
-        ranges[i].result = result[i];
-        if (bad[i] != SIZE_MAX && !reported) {
-            // the lowest-index failed range: a cached reader's text for the frame
-            frame_error(r, true, V.status[bad[i]], V.fail_at[bad[i]], P.frames[bad[i]], 0, 0, errbuf);
-            reported = true;
-        }
-    }
-    return (ssize_t)ok;
+    if (off <= img->size && len <= img->size - off)
+        return true;
+    set_error(J.err, "unexpected EOF");
+    return false;
 }
 
-// An asynchronous call grows buffers for ALL of the lane's idle slots and call
-// tables at once, to what its largest batch needs (submit_gather's sizes, LZ4
-// with a device destination): growing waits for the device, and a slot grown
-// only when a later call reaches it would make that call wait for the caller's
-// stream in the middle of a pipeline that the first call had warmed up.  Slots
-// and tables with work in flight are left alone (their turn comes after their
-// drain).  Best effort: a failure here is reported by the batch that needs
-// the buffer.
-void grow_idle_for_async(VecJob &V, DeviceCtx &g, size_t table_up, size_t table_total)
+bool zsk::ensure_lanes(zseek_reader *r, char *errbuf)
 {
-    zseek_reader *r = V.J.r;
-    const SeekTable &st = r->st;
-    const RangePlan &P = *V.P;
-    const DeviceImage *const img = r->img;
-    const bool ck = r->verify && st.checksum_flag;
-    uint64_t up = 0, out = 0, items = 0;
-    size_t nmax = 0;
-    std::vector<FrameDesc> desc;
-    for (const PlanBatch &b : P.batches) {
-        const size_t n = b.t1 - b.t0, nseg = b.s1 - b.s0;
-        desc.resize(n);
-        uint64_t c = 0;
-        for (size_t i = 0; i < n; i++) {
-            const size_t f = P.frames[b.t0 + i];
-            desc[i].c_off = img ? st.c_off[f] + img->bias : c;
-            desc[i].c_size = (uint32_t)st.csize(f);
-            c += desc[i].c_size;
-        }
-        const uint64_t doff = img ? 0 : (c + 256 + 255) & ~255ull;
-        up = std::max<uint64_t>(up, doff + n * sizeof(FrameDesc) + nseg * sizeof(GatherSeg) +
-                                        (nseg + 1) * sizeof(uint64_t));
-        out = std::max<uint64_t>(out, (b.d_bytes + 255) & ~255ull);
-        items = std::max(items, split_items_needed(desc.data(), (uint32_t)n));
-        nmax = std::max(nmax, n);
+    if (r->devices.empty())
+        r->devices = default_devices();
+    if (r->devices.empty()) {
+        set_error(errbuf, "no HIP device available");
+        return false;
     }
-    const bool split = lz4_pick_engine((uint32_t)nmax) != ENGINE_WAVE;
-    char err[ZSEEK_ERRBUF_SIZE];
-    for (Slot &s : g.slot) {
-        if (s.pending || !nmax)
-            continue;
-        (void)s.reserve(up, out, 0, nmax, ck, err);
-        // (on the slot's own, idle stream: its wait is no wait; the scratch's
-        // first memset is complete before the caller's stream uses it)
-        if (split && split_scratch_reserve(&s.split, (uint32_t)nmax, items, s.stream) == 0)
-            (void)hipStreamSynchronize(s.stream);
-        (void)hipGetLastError();
-    }
-    for (CallTable &c : g.call)
-        if (!c.pending)
-            (void)c.reserve(table_up, table_total, err);
+    while (r->lanes.size() < r->devices.size())
+        r->lanes.emplace_back(new DeviceCtx());
+    for (size_t i = 0; i < r->devices.size(); i++)
+        if (!r->lanes[i]->init(r->devices[i], errbuf))
+            return false;
+    return true;
 }
 
-// zsk_preadv_device_async (zseek_hip.h): preadv_frames' batches queued on the
-// caller's stream, one after the other, and behind the last one
-// range_result_kernel, which leaves in d_result what range_results computes on
-// the host.  Nothing is waited for except a slot or a call table that an
-// earlier asynchronous batch still uses (Slot::drain, CallTable::drain) and
-// buffers that have to grow.
-ssize_t preadv_async(zseek_reader *r, void *d_buf, const zsk_range_t *ranges, size_t nranges, int64_t *d_result,
-                     hipStream_t q, void *call_data, char *errbuf)
+// The reader's stats fields that change (cache, staging) -> the lock-free
+// snapshot zseek_reader_stats reads; called under the exclusive lock.
+void zsk::publish_stats(zseek_reader *r)
 {
-    if (!r) {
-        set_error(errbuf, "invalid reader");
-        return -1;
-    }
-    // the call reuses pinned staging that the host rewrites: it must never
-    // end up in a graph
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(q, &cap);
-    if ((ce == hipSuccess && cap != hipStreamCaptureStatusNone) || ce == hipErrorStreamCaptureImplicit) {
-        (void)hipGetLastError();
-        set_error(errbuf, "asynchronous read: stream is capturing");
-        return -1;
-    }
-    (void)hipGetLastError();   // (no device: reported below, where one is needed)
-    if (r->type != ZSEEK_LZ4) {
-        // zsk_zstd_decode_frames' plan synchronizes
-        set_error(errbuf, "asynchronous read: zstd is not supported");
-        return -1;
-    }
-    if (nranges == 0 && !d_result)
-        return 0;
-    if (!ranges && nranges) {
-        set_error(errbuf, "invalid ranges");
-        return -1;
-    }
-    if (!d_result) {
-        set_error(errbuf, "invalid result buffer");
-        return -1;
-    }
-    const SeekTable &st = r->st;
-    std::vector<RangeReq> req(nranges);
-    for (size_t i = 0; i < nranges; i++)
-        req[i] = {ranges[i].offset, ranges[i].count, ranges[i].dst_off};
-    DeviceGuard keep_device;
-    std::unique_lock<std::shared_mutex> guard(r->lock);
-    struct Publish {
-        zseek_reader *r;
-        ~Publish() { publish_stats(r); }
-    } publish{r};
-    const size_t nframes = st.frames();
-    const uint64_t zero = 0;
-    const uint64_t *const d_off = nframes ? st.d_off.data() : &zero;
-    // (the batches are preadv_frames': see there for the device image's span cut)
-    const RangePlan P = r->img && nframes ? plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes,
-                                                        st.c_off.data(), (uint64_t)std::min<size_t>(r->batch_bytes, SIZE_MAX / 4) * 4)
-                                          : plan_ranges(req.data(), nranges, d_off, nframes, r->batch_bytes);
-    if (!d_buf && !P.segs.empty()) {
-        set_error(errbuf, "invalid buffer");
-        return -1;
-    }
-    for (const PlanBatch &b : P.batches)
-        if (b.s1 - b.s0 >= 0xFFFFFFFFull || b.t1 - b.t0 >= 0x7FFFFFFFull) {
-            set_error(errbuf, "too many ranges");
-            return -1;
-        }
-    if (!ensure_lanes(r, errbuf))
-        return -1;
-    DeviceCtx &g = *r->lanes[0];
-    (void)hipSetDevice(g.device);
-    if (nranges == 0) {   // d_result[0] = 0 alone
-        if (launch_range_result(nullptr, nullptr, nullptr, 0, d_result, q) == 0)
-            return 0;
-        set_error(errbuf, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
-        return -1;
-    }
-    // From here on a failure still leaves the stream's consumer an answer:
-    // every result and the count -1.
-    VecJob V;
-    V.P = &P;
-    V.buf = static_cast<uint8_t *>(d_buf);
-    V.device_dst = true;
-    V.async = true;
-    V.q = q;
-    V.J.r = r;
-    V.J.g = &g;
-    V.J.call_data = call_data;
-    CallTable &c = g.call[g.async_call];
-    g.async_call = (g.async_call + 1) % kSlots;
-    const size_t T = P.frames.size();
-    // rows, t_doff (the upload, which moves whole 16-byte pieces), statuses
-    const size_t rows_bytes = nranges * sizeof(RangeRow), up = rows_bytes + T * sizeof(uint64_t);
-    const size_t st_at = (up + 15) & ~(size_t)15;
-    grow_idle_for_async(V, g, up, st_at + T * sizeof(int32_t));
-    // (a host wait when this table's previous call, kSlots calls ago, has not
-    // finished: the host rewrites its pinned staging)
-    bool ok = c.reserve(up, st_at + T * sizeof(int32_t), V.J.err);
+    r->snap_cache_memory.store(r->cache ? r->cache->memory_usage() : 0, std::memory_order_relaxed);
+    r->snap_cached_frames.store(r->cache ? r->cache->entries() : 0, std::memory_order_relaxed);
+    size_t buffered = 0;
+    for (auto &l : r->lanes)
+        buffered += l->host_bytes();
+    r->snap_buffered.store(buffered, std::memory_order_relaxed);
+}
+
+hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
+{
+    // per-frame status then fail_at, back to back (one download for both)
+    uint32_t *const d_fail = reinterpret_cast<uint32_t *>(s.d_status + a.n);
     hipError_t e = hipSuccess;
-    if (ok) {
-        const RangeTable tab = build_range_table(P, req.data(), nranges, d_off, nframes);
-        memcpy(c.h, tab.rows.data(), rows_bytes);
-        if (T)
-            memcpy(c.h + rows_bytes, tab.t_doff.data(), T * sizeof(uint64_t));
-        V.d_call_status = reinterpret_cast<int32_t *>(c.d + st_at);
-        if (upload_small(c.d, c.h, c.h_dev, up, q) != 0)
+    if (a.type == ZSEEK_ZSTD) {
+        // (a request's few frames are planned on the host from the pinned
+        // span -- no plan launch, no synchronization between plan and decode)
+        if ((a.zplan ? zstd_decode_frames_planned(*a.zplan, a.d_plan, a.d_desc, a.n, a.comp, s.d_out, s.d_status,
+                                                  &s.zs, a.q, d_fail, a.stop_last)
+                     : zstd_decode_frames(a.d_desc, a.n, a.comp, s.d_out, s.d_status, &s.zs, a.q, d_fail,
+                                          a.stop_last)) != 0)
             e = hipErrorLaunchFailure;
-        // a batch that is never queued reads as failed
-        if (e == hipSuccess && T)
-            e = hipMemsetD32Async((hipDeviceptr_t)V.d_call_status, ST_NOT_RUN, T, q);
-        if (e != hipSuccess) {
-            set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(e));
-            ok = false;
-        }
+    } else if (lz4_wave_batch(a.type, a.n)) {
+        // (preset for the wave engine alone: the two-phase decoder's plan
+        // kernel initializes both itself, the zstd sequence kernel writes both
+        // for every frame)
+        e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, a.n, a.q);
+        if (e == hipSuccess)
+            e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, a.n, a.q);
+        if (e == hipSuccess && launch_lz4_wave(a.d_desc, a.n, a.comp, s.d_out, s.d_status, d_fail, a.q) != 0)
+            e = hipErrorLaunchFailure;
+    } else if (a.h_desc && split_scratch_reserve(&s.split, a.n, split_items_needed(a.h_desc, a.n), a.q) != 0) {
+        e = hipErrorOutOfMemory;
+    } else if (launch_lz4_split(a.d_desc, a.n, a.comp, s.d_out, s.d_status, d_fail, a.q, &s.split, ROUTE_AUTO, 15, 0,
+                                a.stop_last, a.max_dsize, a.post, a.posted, a.in_order, !a.in_order) != 0) {
+        e = hipErrorLaunchFailure;
     }
-    // the batches take the lane's slots round robin; a slot whose earlier
-    // asynchronous batch is still in flight is waited for (submit_gather)
-    for (size_t bi = 0; ok && bi < P.batches.size(); bi++) {
-        Slot &s = g.slot[g.async_slot];
-        g.async_slot = (g.async_slot + 1) % kSlots;
-        ok = submit_gather(V, s, bi);
+    // seek-table checksums (descriptor bit 7) when asked for: XXH64 low 32
+    // bits of every decoded frame, on the GPU (frame_check.hip)
+    if (e == hipSuccess && a.d_want) {
+        if (a.d_want == s.d_ck)
+            e = hipMemcpyAsync(s.d_ck, s.h_ck, a.n * sizeof(uint32_t), hipMemcpyHostToDevice, a.q);
+        if (e == hipSuccess && launch_frame_checksums(a.d_desc, a.n, s.d_out, a.d_want, s.d_status, a.q) != 0)
+            e = hipErrorLaunchFailure;
     }
-    if (ok && launch_range_result(reinterpret_cast<const RangeRow *>(c.d),
-                                  reinterpret_cast<const uint64_t *>(c.d + rows_bytes), V.d_call_status, nranges,
-                                  d_result, q) != 0) {
-        set_error(V.J.err, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
-        ok = false;
-    }
-    if (!ok)
-        (void)hipMemsetAsync(d_result, 0xFF, (nranges + 1) * sizeof(int64_t), q);
-    // the table is in use until the stream passes this point
-    if (c.done && !(c.pending = hipEventRecord(c.done, q) == hipSuccess))
-        (void)hipStreamSynchronize(q);
-    if (!ok) {
-        set_error(errbuf, "%s", V.J.err);
-        return -1;
-    }
-    return 0;
+    return e;
 }
-
-// zsk_preadv_device_indirect (zseek_hip.h): a vectored read of a device image
-// whose ranges are in device memory.  The plan is computed on the device
-// (range_plan_dev.hip) from the resident seek table; the host sizes every
-// buffer and grid by its bounds -- nranges, max_frames, the file's largest
-// frame -- and sends nothing but kernel arguments.  One batch: the touched
-// frames (at most max_frames, then padding descriptors) decoded in place from
-// the image into the slot's staging, gathered into d_buf, the results by
-// range_result_kernel and the plan's fix kernel.  The slot and the call table
-// are taken in turn and left pending like preadv_async's.
-ssize_t preadv_indirect(zseek_reader *r, void *d_buf, size_t buf_size, const zsk_range_t *d_ranges, size_t nranges,
-                        size_t max_frames, int64_t *d_result, hipStream_t q, char *errbuf)
-{
-    if (!r) {
-        set_error(errbuf, "invalid reader");
-        return -1;
-    }
-    const DeviceImage *const img = r->img;
-    if (!img) {
-        set_error(errbuf, "device-planned read: needs a device image");
-        return -1;
-    }
-    if (r->type != ZSEEK_LZ4) {
-        set_error(errbuf, "device-planned read: zstd is not supported");
-        return -1;
-    }
-    // (scratch sized per call and reused: never in a graph)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(q, &cap);
-    if ((ce == hipSuccess && cap != hipStreamCaptureStatusNone) || ce == hipErrorStreamCaptureImplicit) {
-        (void)hipGetLastError();
-        set_error(errbuf, "device-planned read: stream is capturing");
-        return -1;
-    }
-    (void)hipGetLastError();
-    if (nranges == 0 && !d_result)
-        return 0;
-    if (nranges && !d_ranges) {
-        set_error(errbuf, "invalid ranges");
-        return -1;
-    }
-    if (!d_result) {
-        set_error(errbuf, "invalid result buffer");
-        return -1;
-    }
-    if (nranges && max_frames == 0) {
-        set_error(errbuf, "device-planned read: max_frames is 0");
-        return -1;
-    }
-    if (nranges && buf_size && !d_buf) {
-        set_error(errbuf, "invalid buffer");
-        return -1;
-    }
-    // (the gather takes a 32-bit segment count, the decode a 31-bit frame count)
-    if (max_frames >= 0x7FFFFFFFull || nranges >= 0xFFFFFFFFull) {
-        set_error(errbuf, "too many ranges");
-        return -1;
-    }
-    const SeekTable &st = r->st;
-    DeviceGuard keep_device;
-    std::unique_lock<std::shared_mutex> guard(r->lock);
-    struct Publish {
-        zseek_reader *r;
-        ~Publish() { publish_stats(r); }
-    } publish{r};
-    if (nranges && img->max_dsize && max_frames > r->batch_bytes / img->max_dsize) {
-        set_error(errbuf, "device-planned read: max_frames frames exceed the batch size");
-        return -1;
-    }
-    // (a range is one segment of the staging, and a segment's length a u32)
-    if (nranges && (uint64_t)max_frames * img->max_dsize > 0xFFFFFFFFull) {
-        set_error(errbuf, "device-planned read: max_frames frames exceed 4 GiB");
-        return -1;
-    }
-    // (a table that puts frames past the image's end: image_span's refusal,
-    // once for the whole table -- its prefix sums only grow)
-    if (st.c_off.back() > img->size) {
-        set_error(errbuf, "unexpected EOF");
-        return -1;
-    }
-    if (!ensure_lanes(r, errbuf))
-        return -1;
-    DeviceCtx &g = *r->lanes[0];
-    (void)hipSetDevice(g.device);
-    if (nranges == 0) {   // d_result[0] = 0 alone
-        if (launch_range_result(nullptr, nullptr, nullptr, 0, d_result, q) == 0)
-            return 0;
-        set_error(errbuf, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
-        return -1;
-    }
-    const size_t nframes = st.frames();
-    const bool ck = r->verify && st.checksum_flag;
-    const PlanLayout L = plan_layout(nranges, max_frames, nframes, ck);
-    const PlanTables T{img->d_coff, img->d_doff, ck ? img->d_ck : nullptr, nframes, img->bias};
-    const uint32_t M = (uint32_t)max_frames;
-    const bool wave = lz4_pick_engine(M) == ENGINE_WAVE;
-    Slot &s = g.slot[g.async_slot];
-    g.async_slot = (g.async_slot + 1) % kSlots;
-    CallTable &c = g.call[g.async_call];
-    g.async_call = (g.async_call + 1) % kSlots;
-    char err[ZSEEK_ERRBUF_SIZE] = {0};
-    // (host waits: a slot or table whose earlier asynchronous work has not
-    // finished, and buffers that have to grow)
-    s.drain();
-    bool ok = c.reserve(0, L.total, err) && s.reserve(0, std::max<size_t>((size_t)max_frames * img->max_dsize, 16), 0, max_frames, false, err);
-    // the parse scratch by the plan's scan layout: max_frames frames of at most
-    // the file's largest compressed size, however far apart they lie
-    if (ok && !wave && split_scratch_reserve(&s.split, M, (uint64_t)M * slots_of(img->max_csize), q) != 0) {
-        set_error(err, "allocate GPU decode buffers failed");
-        ok = false;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        set_error(errbuf, "%s", err);
-        return -1;   // (nothing queued)
-    }
-    // From here on a failure still leaves the stream's consumer an answer:
-    // every result and the count -1.
-    const FrameDesc *const d_desc = reinterpret_cast<const FrameDesc *>(c.d + L.desc);
-    uint32_t *const d_fail = reinterpret_cast<uint32_t *>(s.d_status + M);
-    s.f0 = s.f1 = 0;
-    s.h_from = s.h_len = 0;
-    s.flagged = false;
-    ok = launch_indirect_plan(c.d, L, T, d_ranges, nranges, buf_size, max_frames, q) == 0;
-    if (ok && wave)
-        ok = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, M, q) == hipSuccess &&
-             hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, M, q) == hipSuccess &&
-             launch_lz4_wave(d_desc, M, img->base, s.d_out, s.d_status, d_fail, q) == 0;
-    else if (ok)
-        ok = launch_lz4_split(d_desc, M, img->base, s.d_out, s.d_status, d_fail, q, &s.split, ROUTE_AUTO, 15, 0,
-                              0xFFFFFFFFu, img->max_dsize, nullptr, nullptr, false, true) == 0;
-    if (ok && ck)
-        ok = launch_frame_checksums(d_desc, M, s.d_out, reinterpret_cast<const uint32_t *>(c.d + L.ck), s.d_status,
-                                    q) == 0;
-    // (no host total: the gather's scan launch reads the segments' on the device)
-    if (ok && d_buf)
-        ok = launch_range_gather(reinterpret_cast<const GatherSeg *>(c.d + L.segs), nullptr, (uint32_t)L.seg_cap, 0,
-                                 s.d_out, static_cast<uint8_t *>(d_buf), s.d_status, q) == 0;
-    if (ok)
-        ok = launch_range_result(reinterpret_cast<const RangeRow *>(c.d + L.rows),
-                                 reinterpret_cast<const uint64_t *>(c.d + L.t_doff), s.d_status, nranges, d_result,
-                                 q) == 0 &&
-             launch_indirect_fix(c.d, L, nranges, d_result, q) == 0;
-    if (!ok) {
-        set_error(err, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipMemsetAsync(d_result, 0xFF, (nranges + 1) * sizeof(int64_t), q);
-    }
-    // the slot and the table are in use until the stream passes this point
-    s.pending = hipEventRecord(s.done, q) == hipSuccess;
-    c.pending = s.pending && hipEventRecord(c.done, q) == hipSuccess;
-    if (!s.pending || !c.pending)
-        (void)hipStreamSynchronize(q);
-    if (!ok) {
-        set_error(errbuf, "%s", err);
-        return -1;
-    }
-    g.batches++;   // (frames_decoded / bytes_decoded: the host never learns them)
-    return 0;
-}
-
-}   // namespace
 
 // ---------------------------------------------------------------------------
 // pread / read / stats (ref decompress.c:806-891)
@@ -2009,44 +1194,6 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_pread_device(zseek_reader_t *reader, void *d
         return 0;
     }
     return pread_frames(reader, d_buf, count, offset, call_data, errbuf, true);
-}
-
-// Vectored reads (zseek_hip.h): many ranges, one decode grid per batch.
-extern "C" ZSEEK_EXPORT ssize_t zsk_preadv(zseek_reader_t *reader, void *buf, zsk_range_t *ranges, size_t nranges,
-                                           void *call_data, char *errbuf)
-{
-    return preadv_frames(reader, buf, ranges, nranges, call_data, errbuf, false);
-}
-
-extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf, zsk_range_t *ranges,
-                                                  size_t nranges, void *call_data, char *errbuf)
-{
-    return preadv_frames(reader, d_buf, ranges, nranges, call_data, errbuf, true);
-}
-
-extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf, const zsk_range_t *ranges,
-                                                        size_t nranges, int64_t *d_result, void *stream,
-                                                        void *call_data, char *errbuf)
-{
-    return preadv_async(reader, d_buf, ranges, nranges, d_result, static_cast<hipStream_t>(stream), call_data,
-                        errbuf);
-}
-
-extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *reader, void *d_buf, size_t buf_size,
-                                                           const zsk_range_t *d_ranges, size_t nranges,
-                                                           size_t max_frames, int64_t *d_result, void *stream,
-                                                           char *errbuf)
-{
-    return preadv_indirect(reader, d_buf, buf_size, d_ranges, nranges, max_frames, d_result,
-                           static_cast<hipStream_t>(stream), errbuf);
-}
-
-extern "C" ZSEEK_EXPORT int zsk_gather_segments(const zsk_segment_t *d_seg, uint32_t nseg, const void *d_src,
-                                                void *d_dst, const int32_t *d_status, void *stream)
-{
-    return launch_range_gather(reinterpret_cast<const GatherSeg *>(d_seg), nullptr, nseg, 0,
-                               static_cast<const uint8_t *>(d_src), static_cast<uint8_t *>(d_dst), d_status,
-                               static_cast<hipStream_t>(stream));
 }
 
 // Writes the first `size` bytes of the counters (at most sizeof): a caller

@@ -1,6 +1,6 @@
 """Vectored reads on the GPU: zsk_gather_segments (csrc/range_gather.hip) on
 its own, then zsk_preadv / zsk_preadv_device through the reader
-(csrc/reader.cpp's gathered batches, planned by csrc/range_plan.h).
+(csrc/reader_vec.cpp's gathered batches, planned by csrc/range_plan.h).
 
 Expected bytes are numpy slices of the source buffer or of the golden files'
 payloads, never the library's own output -- except where a corrupted frame

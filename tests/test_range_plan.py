@@ -3,7 +3,7 @@ libzseek_amd/csrc/range_plan.h's pure functions -- the touched frames, their
 runs of adjacent frames (one pread each), the batches, the (range, frame)
 segments the gather kernel moves, and the per-range results from the frames'
 statuses -- plus the entry points' argument checks, which need no device.
-reader.cpp's vectored path calls exactly these."""
+reader_vec.cpp calls exactly these."""
 from __future__ import annotations
 
 import ctypes as C
