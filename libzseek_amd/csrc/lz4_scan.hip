@@ -375,6 +375,17 @@ __device__ __forceinline__ void fast_br(Scan &L)
     }
 }
 
+// A length-extension chain is re-parsed from its sequence's first byte until
+// the ring holds all of it, and the fill stops short of ip + kRing - 16 (sub):
+// a chain that reaches past where the fill stopped (80 to 111 bytes in, a
+// length of 20,000 to 28,000 and more) would wait for the launch's step
+// limit.  The wave kernel decodes such a frame.
+__device__ __forceinline__ void chain_wait(Scan &L, uint32_t p)
+{
+    if (L.cx0 + p >= L.fill && L.fill + 32 > L.cx0 + L.ip + kRing - 16)
+        finish(L, ST_NOT_RUN);
+}
+
 // ---- slow step: byte at a time, every rule (parse_block / parse_frame) -------
 // Returns with the lane waiting (phase unchanged) when bytes are not yet in
 // the ring.
@@ -403,8 +414,10 @@ __device__ __forceinline__ void slow(Scan &L)
                     fail_block(L);
                     return;
                 }
-                if (!have(L, p, 1))
+                if (!have(L, p, 1)) {
+                    chain_wait(L, p);
                     return;   // re-parsed from the token next time
+                }
                 s = rb(L, p++);
                 lit += s;
             } while (s == 255);
@@ -453,8 +466,10 @@ __device__ __forceinline__ void slow(Scan &L)
                     fail_block(L);
                     return;
                 }
-                if (!have(L, p, 1))
+                if (!have(L, p, 1)) {
+                    chain_wait(L, p);
                     return;
+                }
                 s = rb(L, p++);
                 ml += s;
                 if (p >= L.iend - (kLastLiterals - 1)) {

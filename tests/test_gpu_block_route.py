@@ -15,9 +15,9 @@ and bytes (oracle/lz4_oracle.c decode_frame, liblz4
 1.9.3 LZ4F_decompress semantics) and the wave kernel's status codes."""
 import numpy as np
 import pytest
-import xxhash
 
 from conftest import golden_file
+from lz4_craft import check as _check, decode as _decode, lz4f_frame as _frame
 
 pytestmark = pytest.mark.gpu
 
@@ -42,62 +42,6 @@ def _split(frame: bytes):
         blocks.append((h, frame[p: p + n]))
         p += n + (4 if flg & 0x10 else 0)
     return flg, bd, hdr, blocks
-
-
-def _frame(blocks, flg=0x60, bd=0x40, content_size=None, dict_id=None, tail=b""):
-    """An LZ4F frame (magic, descriptor, header checksum) of the given blocks:
-    bytes payloads are stored blocks, (h, payload) pairs are copied."""
-    if content_size is not None:
-        flg |= 8
-    if dict_id is not None:
-        flg |= 1
-    desc = bytes([flg, bd])
-    if content_size is not None:
-        desc += int(content_size).to_bytes(8, "little")
-    if dict_id is not None:
-        desc += int(dict_id).to_bytes(4, "little")
-    out = bytearray(b"\x04\x22\x4d\x18" + desc + bytes([(xxhash.xxh32(desc).intdigest() >> 8) & 0xFF]))
-    for b in blocks:
-        if isinstance(b, (bytes, bytearray)):
-            out += (len(b) | 0x80000000).to_bytes(4, "little") + bytes(b)
-        else:
-            out += b[0].to_bytes(4, "little") + b[1]
-    out += b"\0\0\0\0" + tail
-    return bytes(out)
-
-
-def _decode(zs, gpu, frames, dsizes, engine):
-    import torch
-    n = len(frames)
-    c = np.cumsum([0] + [len(f) for f in frames])
-    d = np.cumsum([0] + list(dsizes))
-    desc = np.zeros(n, dtype=[("c_off", "<u8"), ("d_off", "<u8"), ("c_size", "<u4"), ("d_size", "<u4")])
-    desc["c_off"], desc["d_off"] = c[:-1], d[:-1]
-    desc["c_size"], desc["d_size"] = np.diff(c), np.asarray(dsizes)
-    td = torch.from_numpy(desc.view(np.uint8).copy()).to(gpu)
-    comp = torch.zeros(int(c[-1]) + 256, dtype=torch.uint8, device=gpu)
-    comp[: int(c[-1])].copy_(torch.from_numpy(np.frombuffer(b"".join(frames), np.uint8).copy()))
-    out = torch.zeros(max(int(d[-1]), 1), dtype=torch.uint8, device=gpu)
-    status = torch.full((n,), -1, dtype=torch.int32, device=gpu)
-    zs.decode_frames(td, comp, out, status, engine=engine)
-    torch.cuda.synchronize()
-    o = out.cpu().numpy().tobytes()
-    return [o[int(d[i]): int(d[i + 1])] for i in range(n)], status.cpu().tolist()
-
-
-def _check(zs, oracle, gpu, frames, dsizes, engine="block"):
-    """block route == oracle (status, bytes of OK frames) and == wave statuses"""
-    got, st = _decode(zs, gpu, frames, dsizes, engine)
-    _, st_w = _decode(zs, gpu, frames, dsizes, "wave")
-    assert st == st_w
-    for i, (f, ds) in enumerate(zip(frames, dsizes)):
-        ost, obytes, _, _ = oracle.decode_frame(f, ds)
-        if ost == 0 and len(obytes) == ds:
-            assert st[i] == 0, (i, zs.status_string(st[i]))
-            assert got[i] == obytes, i
-        else:
-            assert st[i] != 0, i
-    return st
 
 
 @pytest.fixture(scope="module")
