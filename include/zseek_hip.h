@@ -43,6 +43,11 @@
  *                            the GPU for frames that are compressed there.
  *   zsk_write_device       — zseek_write (compress.c:650-833) for bytes that
  *                            are already in device memory.
+ *   zsk_zstd_compress_frames, zsk_zstd_build_image — no reference function:
+ *                            zstd frames written on the GPU in a fixed format
+ *                            subset (valid zstd, not libzstd's bytes), and a
+ *                            seekable zstd file built from them in device
+ *                            memory.
  */
 #ifndef ZSEEK_HIP_H
 #define ZSEEK_HIP_H
@@ -538,6 +543,40 @@ ZSEEK_EXPORT int zsk_lz4_compress_frames(const zsk_compress_desc_t *d_desc,
     int level, void *d_scratch, void *stream);
 
 /*
+ * zstd frame compression on the GPU.  Each descriptor becomes one valid zstd
+ * frame (RFC 8878) that libzstd decodes to the input; the bytes are NOT
+ * libzstd's at any level, there is one effort level and no level parameter.
+ * The format subset (csrc/zstd_enc_dev.h): a single-segment header with the
+ * content size always present (ZSK_COMPRESS_CONTENT_SIZE is ignored) and no
+ * dictionary id; blocks of 128 KiB of input, each encoded on its own --
+ * Compressed when that is smaller, RLE for one repeated byte, Raw otherwise;
+ * literals Raw, RLE or Huffman (code lengths <= 11, the tree as direct 4-bit
+ * weights, so literals that hold a byte above 128 are stored Raw:
+ * FSE-compressed weight descriptions are not written); sequences over the
+ * predefined LL / OF / ML tables with every offset coded as offset + 3 (no
+ * repeat offsets, no repeated or custom tables).  A 0-byte frame is the header
+ * and one empty last Raw block (9 bytes).  ZSK_COMPRESS_CONTENT_CHECKSUM in a
+ * descriptor's flags ends its frame with the low 32 bits of XXH64 (seed 0) of
+ * its content.  src_size <= ZSK_ZSTD_COMPRESS_MAX_FRAME; a larger frame is
+ * refused with c_size 0 and its slot is left untouched.
+ *
+ * zsk_zstd_compress_frames follows zsk_lz4_compress_frames' contract:
+ * asynchronous on @stream, dst_off 16-byte aligned, every slot at least
+ * ZSK_ZSTD_COMPRESS_BOUND(src_size) bytes (all blocks Raw) and nothing written
+ * outside it, no source byte read outside the frame, nframes == 0 returns 0,
+ * a @d_scratch smaller than zsk_zstd_compress_scratch_size(nframes, total
+ * source bytes) returns -1.  The same input gives the same bytes on every run.
+ */
+#define ZSK_ZSTD_COMPRESS_MAX_FRAME (1u << 22)
+#define ZSK_COMPRESS_CONTENT_CHECKSUM 2u
+#define ZSK_ZSTD_COMPRESS_BOUND(n) \
+    ((9 + 3 * ((uint64_t)(n) ? (((uint64_t)(n)) + 131071) >> 17 : 1) + ((uint64_t)(n)) + 4 + 15) & ~(uint64_t)15)
+ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size(uint32_t nframes, uint64_t src_bytes);
+ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *d_desc,
+    uint32_t nframes, const void *d_src, void *d_dst, uint32_t *d_csize,
+    void *d_scratch, size_t scratch_size, void *stream);
+
+/*
  * Writer GPU mode: an LZ4 writer's frames of <= 4 MiB are compressed on the
  * GPU (zsk_lz4_compress_frames, on the calling thread's current device) in
  * batches of @batch_bytes input bytes (0: 1 GiB; (size_t)-1: GPU mode off,
@@ -683,6 +722,28 @@ ZSEEK_EXPORT zseek_reader_t *zsk_reader_open_device(const void *d_image, size_t 
 ZSEEK_EXPORT size_t zsk_lz4_image_bound(size_t len, size_t frame_size, unsigned flags);
 ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t frame_size,
     int level, unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * zsk_lz4_build_image for zstd: a complete seekable zstd file built in device
+ * memory from zsk_zstd_compress_frames' frames (the subset described there) by
+ * the same machinery -- pooled slots at ZSK_ZSTD_COMPRESS_BOUND, sizes scanned
+ * and frames packed on the device, the table written there, one host
+ * synchronization at the end.  Frames hold @frame_size bytes (at most
+ * ZSK_ZSTD_COMPRESS_MAX_FRAME), the last one the rest; len == 0 gives the
+ * empty table alone.  ZSK_IMAGE_CHECKSUMS: 12-byte table entries;
+ * ZSK_IMAGE_CONTENT_CHECKSUMS: the same XXH64 word (computed once) also ends
+ * each frame.  @batch_bytes 0: 256 MiB.  zsk_zstd_image_bound: every frame at
+ * its bound plus the table; 0 for frame_size == 0.  Errors are
+ * zsk_lz4_build_image's, under the same conditions (there is no level).  The
+ * result is read as zstd by the reference reader and zsk_reader_open_device.
+ * The pooled scratch is zsk_lz4_build_image's with the zstd compressor's in
+ * place of the LZ4 tables: 512 KiB per frame of a batch, at most 896 MiB.
+ */
+#define ZSK_IMAGE_CONTENT_CHECKSUMS 2u
+ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_size, unsigned flags);
+ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size,
+    unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,
     char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 #ifdef __cplusplus

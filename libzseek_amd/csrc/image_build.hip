@@ -1,16 +1,19 @@
 // image_build.hip — seekable files that live in device memory (gfx950): the
 // glue kernels between the seek table and the decode / compress / gather
-// kernels, and zsk_lz4_build_image.
+// kernels, and zsk_lz4_build_image / zsk_zstd_build_image (one builder over
+// the codec: Codec below).
 //
 // Reading side (zsk_reader_open_device, reader.cpp): image_desc_kernel writes
 // a contiguous batch's FrameDesc[n] from the reader's device-resident prefix
 // sums, so such a batch uploads nothing.
 //
-// Writing side (zsk_lz4_build_image): per batch of frames, on one stream and
+// Writing side (build_image): per batch of frames, on one stream and
 // with no host wait in between,
 //   image_cdesc_kernel   the batch's compressor descriptors (frame i reads
 //                        d_src at i * frame_size, writes slot i)
-//   zsk_lz4_compress_frames, launch_src_checksums   (unchanged kernels)
+//   the codec's frame compressor, launch_src_checksums   (unchanged kernels;
+//                        zstd frames that carry a content checksum take the
+//                        word launch_src_checksums computed)
 //   image_plan_kernel    one workgroup: a 64-bit exclusive scan of the batch's
 //                        compressed sizes on top of the running file offset
 //                        (device memory, so batches chain in stream order);
@@ -66,7 +69,8 @@ __global__ __launch_bounds__(256) void image_desc_kernel(const uint64_t *__restr
 // i.  A piece shorter than fs is the file's last: the writer's buffered frame,
 // whose header carries the content size.
 __global__ __launch_bounds__(256) void image_cdesc_kernel(zsk_compress_desc_t *__restrict__ desc, uint32_t n,
-                                                          uint64_t src0, uint64_t fs, uint64_t len, uint64_t slot)
+                                                          uint64_t src0, uint64_t fs, uint64_t len, uint64_t slot,
+                                                          uint32_t flags, uint32_t tail_flags)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n)
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(256) void image_cdesc_kernel(zsk_compress_desc_t *_
     o.src_off = at;
     o.dst_off = (uint64_t)i * slot;
     o.src_size = (uint32_t)sz;
-    o.flags = sz < fs ? ZSK_COMPRESS_CONTENT_SIZE : 0u;
+    o.flags = flags | (sz < fs ? tail_flags : 0u);
     desc[i] = o;
 }
 
@@ -185,11 +189,23 @@ bool grow(uint8_t **p, size_t *cap, size_t want)
     return true;
 }
 
+// What the builder asks of a codec.
+struct Codec {
+    bool zstd;
+    uint64_t max_frame;
+    uint64_t bound(uint64_t n) const { return zstd ? ZSK_ZSTD_COMPRESS_BOUND(n) : ZSK_LZ4_COMPRESS_BOUND(n); }
+    size_t scratch(uint32_t nframes) const
+    {
+        return zstd ? zstd_compress_scratch_size(nframes) : zsk_lz4_compress_scratch_size(nframes);
+    }
+};
+constexpr Codec kLz4{false, ZSK_LZ4_COMPRESS_MAX_FRAME}, kZstd{true, ZSK_ZSTD_COMPRESS_MAX_FRAME};
+
 struct Geometry {
     uint64_t frames, full, tail, entry, bound;
 };
 
-bool geometry(size_t len, size_t fs, unsigned flags, Geometry *g)
+bool geometry(const Codec &c, size_t len, size_t fs, unsigned flags, Geometry *g)
 {
     if (fs == 0)
         return false;
@@ -197,7 +213,7 @@ bool geometry(size_t len, size_t fs, unsigned flags, Geometry *g)
     g->tail = len % fs;
     g->frames = g->full + (g->tail ? 1 : 0);
     g->entry = (flags & ZSK_IMAGE_CHECKSUMS) ? 12 : 8;
-    g->bound = g->full * ZSK_LZ4_COMPRESS_BOUND(fs) + (g->tail ? ZSK_LZ4_COMPRESS_BOUND(g->tail) : 0) + 8 +
+    g->bound = g->full * c.bound(fs) + (g->tail ? c.bound(g->tail) : 0) + 8 +
                g->entry * g->frames + 9;
     return true;
 }
@@ -232,18 +248,13 @@ int launch_image_desc(const uint64_t *d_coff, const uint64_t *d_doff, uint64_t f
 
 using namespace zsk;
 
-extern "C" ZSEEK_EXPORT size_t zsk_lz4_image_bound(size_t len, size_t frame_size, unsigned flags)
-{
-    Geometry g;
-    return geometry(len, frame_size, flags, &g) ? (size_t)g.bound : 0;
-}
+namespace {
 
-extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t frame_size, int level,
-                                                    unsigned flags, size_t batch_bytes, void *d_image,
-                                                    size_t capacity, char *errbuf)
+ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t frame_size, int level, unsigned flags,
+                    size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
 {
     Geometry g;
-    if (frame_size > ZSK_LZ4_COMPRESS_MAX_FRAME || !geometry(len, frame_size, flags, &g)) {
+    if (frame_size > codec.max_frame || !geometry(codec, len, frame_size, flags, &g)) {
         set_error(errbuf, "build image: invalid frame size");
         return -1;
     }
@@ -271,15 +282,19 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t le
         return -1;
     }
     if (batch_bytes == 0)
-        batch_bytes = frame_size > 65536 ? kBatchLinked : kBatchSmall;
+        batch_bytes = !codec.zstd && frame_size > 65536 ? kBatchLinked : kBatchSmall;
     // frames per batch: batch_bytes of input, and the compressor's scratch
     // (64 KiB per frame) within batch_bytes too, as the writer's GPU mode
     const uint64_t cap_frames = std::min<uint64_t>(kMaxBatchFrames, std::max<uint64_t>(16, batch_bytes / kTableBytes));
     const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, batch_bytes / frame_size),
                                                       std::min<uint64_t>(cap_frames, std::max<uint64_t>(g.frames, 1)));
-    const uint64_t slot = ZSK_LZ4_COMPRESS_BOUND(frame_size);
+    const uint64_t slot = codec.bound(frame_size);
     const uint32_t ew = (uint32_t)(g.entry / 4);
-    const bool ck = ew == 3;
+    // zstd frames that end with their content checksum take the seek table's word
+    const bool in_frame = codec.zstd && (flags & ZSK_IMAGE_CONTENT_CHECKSUMS);
+    const bool ck = ew == 3 || in_frame;
+    const uint32_t cflags = in_frame ? ZSK_COMPRESS_CONTENT_CHECKSUM : 0u;
+    const uint32_t tail_flags = codec.zstd ? 0u : ZSK_COMPRESS_CONTENT_SIZE;
 
     DeviceGuard keep;
     hipStream_t stream = nullptr;
@@ -298,7 +313,7 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t le
     // per batch frame: cdesc (24), seg (24), cum (8, one more), csize, sums (4 + 4)
     const size_t per_frame = sizeof(zsk_compress_desc_t) + sizeof(GatherSeg) + 8 + 4 + 4;
     bool ok = grow(&s->slots, &s->slots_cap, g.frames ? per * slot : 0) &&
-              grow(&s->tables, &s->tables_cap, g.frames ? zsk_lz4_compress_scratch_size(per) : 0) &&
+              grow(&s->tables, &s->tables_cap, g.frames ? codec.scratch(per) : 0) &&
               grow(&s->frames, &s->frames_cap, g.frames ? per * per_frame + 64 : 0) &&
               grow(&s->entries, &s->entries_cap, std::max<size_t>(g.frames * g.entry, 16));
     if (ok && !s->state)
@@ -325,10 +340,11 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t le
     for (uint64_t f = 0; ok && f < g.frames; f += per) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(per, g.frames - f);
         hipLaunchKernelGGL(image_cdesc_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_cdesc, n,
-                           f * (uint64_t)frame_size, (uint64_t)frame_size, (uint64_t)len, slot);
-        ok = hipGetLastError() == hipSuccess &&
-             zsk_lz4_compress_frames(d_cdesc, n, src, s->slots, d_csize, level, s->tables, stream) == 0 &&
-             (!ck || launch_src_checksums(d_cdesc, n, src, d_sums, stream) == 0);
+                           f * (uint64_t)frame_size, (uint64_t)frame_size, (uint64_t)len, slot, cflags, tail_flags);
+        ok = hipGetLastError() == hipSuccess && (!ck || launch_src_checksums(d_cdesc, n, src, d_sums, stream) == 0) &&
+             (codec.zstd ? launch_zstd_compress(d_cdesc, n, src, s->slots, d_csize, s->tables, s->tables_cap,
+                                                in_frame ? d_sums : nullptr, stream)
+                         : zsk_lz4_compress_frames(d_cdesc, n, src, s->slots, d_csize, level, s->tables, stream)) == 0;
         if (!ok)
             break;
         hipLaunchKernelGGL(image_plan_kernel, dim3(1), dim3(kPlanT), 0, stream, d_csize, d_cdesc, d_sums, n, f, ew,
@@ -361,4 +377,31 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t le
         return -1;
     }
     return (ssize_t)size;
+}
+
+}   // namespace
+
+extern "C" ZSEEK_EXPORT size_t zsk_lz4_image_bound(size_t len, size_t frame_size, unsigned flags)
+{
+    Geometry g;
+    return geometry(kLz4, len, frame_size, flags, &g) ? (size_t)g.bound : 0;
+}
+
+extern "C" ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t frame_size, int level,
+                                                    unsigned flags, size_t batch_bytes, void *d_image,
+                                                    size_t capacity, char *errbuf)
+{
+    return build_image(kLz4, d_src, len, frame_size, level, flags, batch_bytes, d_image, capacity, errbuf);
+}
+
+extern "C" ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_size, unsigned flags)
+{
+    Geometry g;
+    return geometry(kZstd, len, frame_size, flags, &g) ? (size_t)g.bound : 0;
+}
+
+extern "C" ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size, unsigned flags,
+                                                     size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
+{
+    return build_image(kZstd, d_src, len, frame_size, 0, flags, batch_bytes, d_image, capacity, errbuf);
 }

@@ -1,0 +1,363 @@
+// zstd_compress.hip — zstd frame compression on the GPU (gfx950):
+// zsk_zstd_compress_frames.  The frames are valid zstd (RFC 8878) that libzstd
+// decodes to the input; they are not libzstd's bytes at any level, and there
+// is one effort level.  The format subset and everything that decides bytes
+// once the matches are known is zstd_enc_dev.h (shared with the CPU shim of
+// tests/test_zstd_enc.py); what it leaves out -- FSE-compressed Huffman
+// weights (so literals holding a byte above 128 are stored Raw), repeat
+// offsets, custom or repeated tables, frames above 4 MiB -- is listed there.
+//
+// Mapping: one single-wave workgroup per frame, the frame's blocks (kZBlock
+// input bytes each) in order, each block independent of the others: a fresh
+// hash table, no matches into earlier blocks.  Workgroups are persistent (at
+// most kGridMax of them walk the batch), so the scratch -- a block's compacted
+// literals and its sequences -- is per workgroup, not per frame.
+//   match      the wave looks at 64 positions a step: every lane hashes the 4
+//              bytes at its position, reads the table (LDS, positions of
+//              earlier steps only) and compares; the lowest lane that matches
+//              wins (__ballot), the wave extends the match 256 bytes a round,
+//              and the step's positions before the next step's start enter the
+//              table by atomicMax -- by value, so the bytes never depend on
+//              which lane arrives first
+//   literals   histogram by LDS atomics while the literals are compacted; one
+//              lane assigns the code lengths; the wave sums each stream's code
+//              bits, which fixes the section's layout; four lanes encode the
+//              four streams
+//   sequences  one lane walks the three FSE states over the predefined
+//              tables, which the workgroup builds in LDS once
+//   assemble   the block is written where it lands: a block's size is known
+//              before the next one starts, so no scan is needed
+// Source bytes are read only inside the frame (a 4-byte read always lies
+// within it); nothing is written outside the slot's ZSK_ZSTD_COMPRESS_BOUND.
+//
+// Algorithmic bytes per frame: n read (+ the literals written and read back)
+// + the frame's compressed size written.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/zseek_hip.h"
+#include "zsk_internal.h"
+#include "zstd_enc_dev.h"
+
+namespace zsk {
+
+namespace {
+
+using namespace zenc;
+
+static_assert(ZSK_ZSTD_COMPRESS_MAX_FRAME == kMaxFrame, "the header's cap");
+static_assert(ZSK_ZSTD_COMPRESS_BOUND(0) == 16 && ZSK_ZSTD_COMPRESS_BOUND(kZBlock + 1) == ((9 + 6 + kZBlock + 1 + 4 + 15) & ~15u),
+              "the header's bound follows kZBlock");
+
+typedef uint32_t u32_ua __attribute__((aligned(1)));
+
+constexpr uint32_t kGridMax = 1792;                   // workgroups that walk a batch: 7 per CU (LDS)
+constexpr uint32_t kSeqMax = kZBlock / kMinMatch;     // sequences a block can hold
+constexpr size_t kWgScratch = kZBlock + (size_t)kSeqMax * sizeof(Seq);
+
+struct Lds {
+    uint32_t tab[1u << kHashLog];    // position + 1 by hash; 0: empty
+    uint32_t count[kHufSyms + 1];    // literal histogram; [kHufSyms]: bytes above 128
+    uint32_t bits[4];                // code bits per Huffman stream
+    uint32_t ws[kHufWorkWords];
+    HufCode huf;
+    SeqTables T;
+    LitPlan plan;
+    uint32_t wants, comp;
+};
+
+__device__ __forceinline__ uint32_t ld4(const uint8_t *p)
+{
+    return *reinterpret_cast<const u32_ua *>(p);
+}
+
+// in[0..n) is one repeated byte (n >= 1).
+__device__ bool one_byte_run(const uint8_t *in, uint32_t n)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint8_t b = in[0];
+    for (uint32_t i = 0; i < n; i += 64) {
+        const bool differs = i + lane < n && in[i + lane] != b;
+        if (__ballot(differs))
+            return false;
+    }
+    return true;
+}
+
+// Literals s[from, from + len) behind lit[nlit), counted.
+__device__ __forceinline__ void take_literals(Lds &L, const uint8_t *s, uint32_t from, uint32_t len, uint8_t *lit,
+                                              uint32_t nlit)
+{
+    for (uint32_t i = threadIdx.x; i < len; i += 64) {
+        const uint32_t c = s[from + i];
+        lit[nlit + i] = (uint8_t)c;
+        atomicAdd(&L.count[c < kHufSyms ? c : kHufSyms], 1u);
+    }
+}
+
+// Block s[b0, b0 + bn) of the frame s at dst; returns its size with the
+// 3-byte header.  Wave-uniform: every lane takes every branch together.
+__device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32_t b0, uint32_t bn, bool last,
+                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq)
+{
+    const uint32_t lane = threadIdx.x;
+    if (bn == 0) {
+        if (lane == 0)
+            block_header(dst, last, kBlockRaw, 0);
+        return 3;
+    }
+    if (one_byte_run(s + b0, bn)) {
+        if (lane == 0) {
+            block_header(dst, last, block_choice(bn, true, 0), bn);
+            dst[3] = s[b0];
+        }
+        return 4;
+    }
+    for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
+        L.tab[i] = 0;
+    for (uint32_t i = lane; i < kHufSyms + 1; i += 64)
+        L.count[i] = 0;
+    if (lane < 4)
+        L.bits[lane] = 0;
+    __syncthreads();
+
+    // ---- match
+    const uint32_t end = b0 + bn;
+    uint32_t anchor = b0, base = b0, nseq = 0, nlit = 0;
+    while (base + kMinMatch <= end) {
+        const uint32_t pos = base + lane;
+        const bool valid = pos + 4 <= end;
+        uint32_t v = 0, h = 0, cand = 0;
+        if (valid) {
+            v = ld4(s + pos);
+            h = match_hash(v);
+            cand = L.tab[h];
+        }
+        const bool hit = valid && cand != 0 && ld4(s + cand - 1) == v;
+        const uint64_t hits = __ballot(hit);
+        if (hits == 0) {
+            if (valid)
+                atomicMax(&L.tab[h], pos + 1);
+            __syncthreads();
+            base += 64;
+            continue;
+        }
+        const int hl = __ffsll((unsigned long long)hits) - 1;
+        const uint32_t mpos = base + (uint32_t)hl, mc = (uint32_t)__shfl((int)cand, hl, 64) - 1;
+        uint32_t ml = 4;
+        for (;;) {   // 4 bytes a lane, 256 a round; a lane at the block's end compares what is left
+            const uint32_t a = mpos + ml + 4 * lane, c = mc + ml + 4 * lane;
+            uint32_t eq = 0;
+            if (a + 4 <= end) {
+                const uint32_t x = ld4(s + a) ^ ld4(s + c);
+                eq = x ? (uint32_t)__builtin_ctz(x) >> 3 : 4u;
+            } else {
+                while (a + eq < end && s[a + eq] == s[c + eq])
+                    eq++;
+            }
+            const uint64_t stop = __ballot(eq < 4);
+            if (stop) {
+                const int j = __ffsll((unsigned long long)stop) - 1;
+                ml += 4 * (uint32_t)j + (uint32_t)__shfl((int)eq, j, 64);
+                break;
+            }
+            ml += 256;
+        }
+        const uint32_t next = mpos + ml;
+        if (valid && pos < next)
+            atomicMax(&L.tab[h], pos + 1);
+        const uint32_t ll = mpos - anchor;
+        take_literals(L, s, anchor, ll, lit, nlit);
+        if (lane == 0)
+            seq[nseq] = Seq{ll, ml, mpos - mc};
+        nseq++;
+        nlit += ll;
+        anchor = base = next;
+        __syncthreads();
+    }
+    take_literals(L, s, anchor, end - anchor, lit, nlit);
+    nlit += end - anchor;
+    __syncthreads();
+
+    // ---- literals: the plan
+    if (lane == 0)
+        L.wants = lit_wants_huf(L.count, L.count[kHufSyms], nlit, L.huf, L.ws, L.plan) ? 1u : 0u;
+    __syncthreads();
+    const uint32_t ns = huf_streams(nlit), seg = huf_segment(nlit);
+    if (L.wants) {
+        for (uint32_t k = 0; k < ns; k++) {
+            const uint32_t a = ns == 4 ? k * seg : 0, b = ns == 4 && k < 3 ? a + seg : nlit;
+            uint32_t sum = 0;
+            for (uint32_t i = a + lane; i < b; i += 64)
+                sum += L.huf.len[lit[i]];
+            atomicAdd(&L.bits[k], sum);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            const uint64_t bits[4] = {L.bits[0], L.bits[1], L.bits[2], L.bits[3]};
+            lit_plan_huf(L.huf, bits, L.plan);
+        }
+        __syncthreads();
+    }
+    const uint32_t mode = L.plan.mode, lsize = L.plan.size;
+    if (lane == 0)
+        L.comp = 0;
+    uint8_t *const body = dst + 3;
+    if (lsize + 1 < bn) {
+        // ---- literals and sequences, where they land
+        if (lane == 0)
+            lit_write_head(L.plan, L.huf, body);
+        if (mode == kLitRaw) {
+            const uint32_t head = lsize - nlit;
+            for (uint32_t i = lane; i < nlit; i += 64)
+                body[head + i] = lit[i];
+        } else if (mode == kLitRle) {
+            if (lane == 0)
+                body[lsize - 1] = lit[0];
+        } else if (lane < ns) {
+            uint32_t off = lsize;   // the streams end the section
+            for (uint32_t k = lane; k < ns; k++)
+                off -= L.plan.stream[k];
+            const uint32_t a = ns == 4 ? lane * seg : 0, b = ns == 4 && lane < 3 ? a + seg : nlit;
+            huf_encode_stream(L.huf, lit + a, b - a, body + off, body + off + L.plan.stream[lane]);
+        }
+        if (lane == 0) {
+            const uint32_t sz = seq_section(L.T, seq, nseq, body + lsize, body + bn);
+            L.comp = sz ? lsize + sz : 0;
+        }
+    }
+    __syncthreads();
+    const uint32_t comp = L.comp;
+    const uint32_t type = block_choice(bn, false, comp);
+    __syncthreads();   // (L.comp is rewritten by the next block)
+    if (type == kBlockCompressed) {
+        if (lane == 0)
+            block_header(dst, last, type, comp);
+        return 3 + comp;
+    }
+    if (lane == 0)
+        block_header(dst, last, kBlockRaw, bn);
+    for (uint32_t i = lane; i < bn; i += 64)
+        body[i] = s[b0 + i];
+    return 3 + bn;
+}
+
+__global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_desc_t *__restrict__ desc,
+                                                           uint32_t nframes, const uint8_t *__restrict__ src,
+                                                           uint8_t *__restrict__ dst, uint32_t *__restrict__ csize,
+                                                           const uint32_t *__restrict__ sums,
+                                                           uint8_t *__restrict__ scratch)
+{
+    __shared__ Lds L;
+    const uint32_t lane = threadIdx.x;
+    if (lane == 0)
+        seq_tables_build(L.T);
+    __syncthreads();
+    uint8_t *const lit = scratch + (size_t)blockIdx.x * kWgScratch;
+    Seq *const seq = reinterpret_cast<Seq *>(lit + kZBlock);
+    for (uint32_t f = blockIdx.x; f < nframes; f += gridDim.x) {
+        const zsk_compress_desc_t d = desc[f];
+        if (d.src_size > kMaxFrame || (d.dst_off & 15)) {
+            if (lane == 0)
+                csize[f] = 0;
+            continue;
+        }
+        const uint8_t *const s = src + d.src_off;
+        uint8_t *const out = dst + d.dst_off;
+        const uint32_t n = d.src_size;
+        const bool ck = (d.flags & ZSK_COMPRESS_CONTENT_CHECKSUM) != 0;
+        if (lane == 0)
+            frame_header(out, n, ck);
+        uint32_t at = frame_header_size(n);
+        const uint32_t nb = frame_blocks(n);
+        for (uint32_t b = 0; b < nb; b++) {
+            const uint32_t b0 = b * kZBlock;
+            at += compress_block(L, s, b0, min(n - b0, kZBlock), b + 1 == nb, out + at, lit, seq);
+        }
+        if (ck) {
+            if (lane < 4)
+                out[at + lane] = (uint8_t)(sums[f] >> (8 * lane));
+            at += 4;
+        }
+        if (lane == 0)
+            csize[f] = at;
+    }
+}
+
+// The descriptors the checksum kernel sees: the frames that ask for a content
+// checksum, the others (and refused ones) as empty frames.
+__global__ __launch_bounds__(256) void zstd_ckdesc_kernel(const zsk_compress_desc_t *__restrict__ desc, uint32_t n,
+                                                          zsk_compress_desc_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    zsk_compress_desc_t d = desc[i];
+    if (!(d.flags & ZSK_COMPRESS_CONTENT_CHECKSUM) || d.src_size > kMaxFrame)
+        d.src_size = 0;
+    out[i] = d;
+}
+
+size_t align256(size_t v)
+{
+    return (v + 255) & ~(size_t)255;
+}
+
+uint32_t grid_of(uint32_t nframes)
+{
+    return std::min(nframes, kGridMax);
+}
+
+}   // namespace
+
+size_t zstd_compress_scratch_size(uint32_t nframes)
+{
+    if (nframes == 0)
+        return 0;
+    return align256((size_t)grid_of(nframes) * kWgScratch) + align256((size_t)nframes * sizeof(zsk_compress_desc_t)) +
+           align256((size_t)nframes * sizeof(uint32_t));
+}
+
+int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst,
+                         uint32_t *d_csize, void *d_scratch, size_t scratch_size, const uint32_t *d_sums,
+                         hipStream_t stream)
+{
+    if (nframes == 0)
+        return 0;
+    if (!d_desc || !d_src || !d_dst || !d_csize || !d_scratch || scratch_size < zstd_compress_scratch_size(nframes))
+        return -1;
+    const uint32_t grid = grid_of(nframes);
+    uint8_t *const wg = static_cast<uint8_t *>(d_scratch);
+    if (!d_sums) {
+        zsk_compress_desc_t *const ckdesc = reinterpret_cast<zsk_compress_desc_t *>(wg + align256((size_t)grid * kWgScratch));
+        uint32_t *const sums = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ckdesc) +
+                                                            align256((size_t)nframes * sizeof(zsk_compress_desc_t)));
+        hipLaunchKernelGGL(zstd_ckdesc_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, d_desc, nframes,
+                           ckdesc);
+        if (hipGetLastError() != hipSuccess || launch_src_checksums(ckdesc, nframes, d_src, sums, stream) != 0)
+            return -1;
+        d_sums = sums;
+    }
+    hipLaunchKernelGGL(zstd_compress_kernel, dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src, d_dst, d_csize,
+                       d_sums, wg);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}   // namespace zsk
+
+extern "C" ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size(uint32_t nframes, uint64_t src_bytes)
+{
+    (void)src_bytes;   // the scratch is per resident workgroup and per frame, not per input byte
+    return zsk::zstd_compress_scratch_size(nframes);
+}
+
+extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *d_desc, uint32_t nframes,
+                                                     const void *d_src, void *d_dst, uint32_t *d_csize,
+                                                     void *d_scratch, size_t scratch_size, void *stream)
+{
+    return zsk::launch_zstd_compress(d_desc, nframes, static_cast<const uint8_t *>(d_src),
+                                     static_cast<uint8_t *>(d_dst), d_csize, d_scratch, scratch_size, nullptr,
+                                     static_cast<hipStream_t>(stream));
+}

@@ -91,6 +91,8 @@ COMPRESS_DESC_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("src_si
                                 ("flags", "<u4")])
 assert COMPRESS_DESC_DTYPE.itemsize == 24
 COMPRESS_CONTENT_SIZE = 1
+COMPRESS_CONTENT_CHECKSUM = 2   # zstd: the frame ends with XXH64's low 32 bits
+ZSTD_COMPRESS_MAX_FRAME = 1 << 22
 # zsk_range_t: one range of a vectored read (result is written by the call)
 RANGE_DTYPE = np.dtype([("offset", "<u8"), ("count", "<u8"), ("dst_off", "<u8"), ("result", "<i8")])
 assert RANGE_DTYPE.itemsize == 32
@@ -118,6 +120,7 @@ EXPORTED = [
     "zsk_gather_segments",
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
+    "zsk_zstd_compress_scratch_size", "zsk_zstd_compress_frames", "zsk_zstd_image_bound", "zsk_zstd_build_image",
 ]
 
 _lib = None
@@ -228,6 +231,16 @@ def lib() -> C.CDLL:
     L.zsk_lz4_build_image.restype = C.c_ssize_t
     L.zsk_lz4_build_image.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_uint, C.c_size_t,
                                       C.c_void_p, C.c_size_t, C.c_char_p]
+    L.zsk_zstd_compress_scratch_size.restype = C.c_size_t
+    L.zsk_zstd_compress_scratch_size.argtypes = [C.c_uint32, C.c_uint64]
+    L.zsk_zstd_compress_frames.restype = C.c_int
+    L.zsk_zstd_compress_frames.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]
+    L.zsk_zstd_image_bound.restype = C.c_size_t
+    L.zsk_zstd_image_bound.argtypes = [C.c_size_t, C.c_size_t, C.c_uint]
+    L.zsk_zstd_build_image.restype = C.c_ssize_t
+    L.zsk_zstd_build_image.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t,
+                                       C.c_void_p, C.c_size_t, C.c_char_p]
     _lib = L
     return L
 
@@ -873,6 +886,93 @@ def lz4_build_image(src, frame_size: int, level: int = 0, checksums: bool = Fals
     n = lib().zsk_lz4_build_image(src.data_ptr() if src.numel() else None, src.numel(), frame_size, level,
                                   IMAGE_CHECKSUMS if checksums else 0, batch_bytes, image.data_ptr(),
                                   image.numel(), err)
+    if n < 0:
+        raise ZseekError(err.value.decode())
+    return image[:n]
+
+
+ZSTD_BLOCK = 131072   # kZBlock (csrc/zstd_enc_dev.h): input bytes per block of a GPU-written zstd frame
+
+
+def zstd_compress_bound(n: int) -> int:
+    """ZSK_ZSTD_COMPRESS_BOUND: output slot bytes for a frame of n bytes."""
+    return (9 + 3 * max(1, -(-n // ZSTD_BLOCK)) + n + 4 + 15) & ~15
+
+
+def zstd_compress_layout(sizes, src_offsets=None, flags=None) -> tuple[np.ndarray, int]:
+    """Descriptors for zsk_zstd_compress_frames, as lz4_compress_layout: slots
+    at ZSK_ZSTD_COMPRESS_BOUND back to back.  -> (COMPRESS_DESC_DTYPE array,
+    dst bytes needed)."""
+    sizes = np.asarray(sizes, np.uint64)
+    n = sizes.size
+    d = np.zeros(n, COMPRESS_DESC_DTYPE)
+    d["src_size"] = sizes
+    if src_offsets is None:
+        src_offsets = np.concatenate(([0], np.cumsum(sizes)[:-1])) if n else sizes
+    d["src_off"] = src_offsets
+    blocks = np.maximum((sizes + np.uint64(ZSTD_BLOCK - 1)) // np.uint64(ZSTD_BLOCK), np.uint64(1))
+    slots = (np.uint64(9) + np.uint64(3) * blocks + sizes + np.uint64(4 + 15)) & ~np.uint64(15)
+    d["dst_off"] = np.concatenate(([0], np.cumsum(slots)[:-1])) if n else slots
+    if flags is not None:
+        d["flags"] = flags
+    return d, int(slots.sum())
+
+
+def zstd_compress_scratch_size(nframes: int, src_bytes: int = 0) -> int:
+    return int(lib().zsk_zstd_compress_scratch_size(nframes, src_bytes))
+
+
+def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None = None) -> None:
+    """zsk_zstd_compress_frames on torch device tensors (async on the current
+    stream): desc = COMPRESS_DESC_DTYPE bytes (uint8), src / dst uint8,
+    csize one int32 per frame (frame sizes out; 0 = refused descriptor)."""
+    import torch
+    n = csize.numel()
+    if desc.numel() != n * 24:
+        raise ValueError("desc must hold 24 bytes per frame")
+    if scratch is None:
+        scratch = torch.empty(max(zstd_compress_scratch_size(n, src.numel()), 1), dtype=torch.uint8,
+                              device=csize.device)
+    for t in (desc, src, dst, csize, scratch):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("zstd_compress_frames needs contiguous device tensors")
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if lib().zsk_zstd_compress_frames(desc.data_ptr(), n, src.data_ptr(), dst.data_ptr(), csize.data_ptr(),
+                                      scratch.data_ptr(), scratch.numel(), stream) != 0:
+        raise ZseekError("zsk_zstd_compress_frames launch failed")
+
+
+IMAGE_CONTENT_CHECKSUMS = 2   # ZSK_IMAGE_CONTENT_CHECKSUMS
+
+
+def _image_flags(checksums: bool, content_checksums: bool) -> int:
+    return (IMAGE_CHECKSUMS if checksums else 0) | (IMAGE_CONTENT_CHECKSUMS if content_checksums else 0)
+
+
+def zstd_image_bound(length: int, frame_size: int, checksums: bool = False) -> int:
+    """zsk_zstd_image_bound: the capacity zsk_zstd_build_image asks for."""
+    return int(lib().zsk_zstd_image_bound(length, frame_size, IMAGE_CHECKSUMS if checksums else 0))
+
+
+def zstd_build_image(src, frame_size: int, checksums: bool = False, content_checksums: bool = False,
+                     batch_bytes: int = 0, image=None):
+    """zsk_zstd_build_image: the uint8 device tensor `src` as a complete
+    seekable zstd file in device memory (synchronous), as lz4_build_image.
+    -> the file, a view of `image`."""
+    import torch
+    if not src.is_cuda or not src.is_contiguous() or src.dtype != torch.uint8:
+        raise ValueError("zstd_build_image needs a contiguous uint8 device tensor")
+    if image is None:
+        image = torch.empty(max(zstd_image_bound(src.numel(), frame_size, checksums), 1), dtype=torch.uint8,
+                            device=src.device)
+    if not image.is_cuda or not image.is_contiguous() or image.dtype != torch.uint8:
+        raise ValueError("zstd_build_image needs a contiguous uint8 device tensor to build in")
+    torch.cuda.current_stream(src.device).synchronize()   # the bytes must be complete
+    err = C.create_string_buffer(ERRBUF)
+    n = lib().zsk_zstd_build_image(src.data_ptr() if src.numel() else None, src.numel(), frame_size,
+                                   _image_flags(checksums, content_checksums), batch_bytes, image.data_ptr(),
+                                   image.numel(), err)
     if n < 0:
         raise ZseekError(err.value.decode())
     return image[:n]
