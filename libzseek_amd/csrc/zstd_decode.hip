@@ -633,7 +633,8 @@ enum : uint32_t {
                   // e: literal count, f: block, g: table logs LL | OF << 4 | ML << 8
     OP_RUN,       // a: literal start, b: bytes (raw / RLE block)
     OP_FBEGIN,    // zstd frame starts: repeat offsets reset
-    OP_FEND,      // a: 1 = content size present, 2 = checksum; b/c: size lo/hi; d: checksum
+    OP_FEND,      // a: 1 = content size present, 2 = checksum (4: the replay's request to check it,
+                  // e/f: the frame's start and length); b/c: size lo/hi; d: checksum
     OP_ERR,       // a: status
     OP_DONE,
 };
@@ -954,6 +955,10 @@ __device__ __forceinline__ uint32_t block_body(ZLds &L, Frame &F, uint32_t p, ui
     const uint32_t wx = stage_win(L, F.I, q);
     auto B = [&](uint32_t i) { return uni(wb(L, wx, F.I, q + i)); };
     uint32_t nseq = B(0);
+    // (a count of 0 written in a 2- or 3-byte form still has its mode byte and
+    // table descriptions read, as ZSTD_decodeSeqHeaders does: only a first
+    // byte of 0 ends the section)
+    const bool tables = nseq != 0;
     if (nseq == 0) {
         if (qe - q != 1)
             return ZE_SRC_WRONG;
@@ -972,7 +977,7 @@ __device__ __forceinline__ uint32_t block_body(ZLds &L, Frame &F, uint32_t p, ui
         q += 1;
     }
     uint32_t tl = 0;
-    if (nseq) {
+    if (tables) {
         if (q + 1 > qe)
             return ZE_SRC_WRONG;
         const uint32_t modes = uni(wb(L, wx, F.I, q));
@@ -1043,10 +1048,7 @@ __device__ __forceinline__ uint32_t decode_entry(ZLds &L, Frame &F, uint32_t cle
 {
     const uint32_t lane = lane_id();
     uint32_t ip = 0, frames = 0;
-    bool summed = false;   // a checksummed frame was decoded: it must be the entry's last
     while (clen - ip >= 5) {
-        if (summed)
-            return ZE_GENERIC;
         uint32_t wx = stage_win(L, F.I, ip);
         auto B = [&](uint32_t i) { return uni(wb(L, wx, F.I, ip + i)); };
         const uint32_t magic = B(0) | B(1) << 8 | B(2) << 16 | B(3) << 24;
@@ -1149,7 +1151,6 @@ __device__ __forceinline__ uint32_t decode_entry(ZLds &L, Frame &F, uint32_t cle
                 wx = stage_win(L, F.I, ip);
                 want = B(0) | B(1) << 8 | B(2) << 16 | B(3) << 24;
                 fl |= 2;
-                summed = true;
                 ip += 4;
             }
         }
@@ -2335,7 +2336,10 @@ __device__ __forceinline__ void seq_body(
     S.k = 0;
     S.cap = icap;
     uint16_t *const mytab = &ftab[CELLS && !ONE ? lane * CELLS : 0];
-    const uint32_t cap = d.d_size;
+    // o and cap count from the start of the entry's current frame, at o0 in the
+    // entry's output (OP_FBEGIN rebases them): libzstd's prefix starts at the
+    // frame, so a match may reach back o + ll bytes and no further
+    uint32_t cap = d.d_size;
     uint32_t o = 0, o0 = 0, rep0 = 1, rep1 = 4, rep2 = 8;
     uint64_t c = 0;
     int32_t st = zerr(ZE_GENERIC);
@@ -2352,14 +2356,14 @@ __device__ __forceinline__ void seq_body(
         for (uint32_t k = 0; k < opn; k++) {
             const ZOp P = op[k];
             uint32_t err = 0;
-            fa = o;
+            fa = o0 + o;
             kstop = k;
             if (P.k == OP_LIT) {
                 // the Huffman kernel runs beside this one: whether this
                 // block's literals decoded is settled by zstd_lit_fix_kernel,
                 // from the item count and output offset kept here
                 op[k].b = S.k;
-                op[k].c = o;
+                op[k].c = o0 + o;
             } else if (P.k == OP_SEQ) {
                 const uint32_t nseq = P.a;
                 uint32_t lp_ = P.d;
@@ -2397,9 +2401,11 @@ __device__ __forceinline__ void seq_body(
                         b.sl = sl;
                         staged = true;
                     }
-                    if (!staged) {   // (ONE: a block's sequences always fit the stage)
+                    if (P.c == 0) {   // sequences counted and no stream: BIT_initDStream's error
+                        err = ZE_CORRUPT;
+                    } else if (!staged) {   // (ONE: a block's sequences always fit the stage)
                         err = ZE_GENERIC;
-                    } else if (P.c == 0 || !sr_init(b, r, sx, P.c)) {
+                    } else if (!sr_init(b, r, sx, P.c)) {
                         err = ZE_CORRUPT;
                     } else {
                         const uint32_t tll = P.g & 15, tof = (P.g >> 4) & 15, tml = (P.g >> 8) & 15;
@@ -2893,12 +2899,19 @@ __device__ __forceinline__ void seq_body(
                 rep0 = 1;
                 rep1 = 4;
                 rep2 = 8;
-                o0 = o;
+                o0 += o;
+                cap -= o;
+                o = 0;
             } else if (P.k == OP_FEND) {
-                if ((P.a & 1) && (uint64_t)(o - o0) != ((uint64_t)P.c << 32 | P.b))
+                if ((P.a & 1) && (uint64_t)o != ((uint64_t)P.c << 32 | P.b))
                     err = ZE_CORRUPT;
-                else if (P.a & 2)
-                    c = (1ull << 63) | ((uint64_t)o0 << 32) | P.d;
+                else if (P.a & 2) {
+                    // a checksum request: the frame's range into its op
+                    op[k].a = P.a | 4;
+                    op[k].e = o0;
+                    op[k].f = o;
+                    c = 1ull << 63;
+                }
             } else if (P.k == OP_ERR) {
                 st = (int32_t)P.a;
                 break;
@@ -3083,78 +3096,96 @@ __device__ __forceinline__ uint64_t xmerge(uint64_t acc, uint64_t v)
 __global__ __launch_bounds__(256) void zstd_check_kernel(const FrameDesc *__restrict__ desc, uint32_t n,
                                                          const uint8_t *__restrict__ out,
                                                          const uint64_t *__restrict__ ck,
+                                                         const uint8_t *__restrict__ ops,
+                                                         const uint64_t *__restrict__ blk_base,
                                                          int32_t *__restrict__ status,
-                                                         uint32_t *__restrict__ fail_at, uint32_t stop_last)
+                                                         uint32_t *__restrict__ fail_at, uint32_t stop_last,
+                                                         uint32_t f0)
 {
     __shared__ uint64_t buf[4][128];
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t f = uni(blockIdx.x * 4 + w);
+    const uint32_t f = uni(blockIdx.x * 4 + w);   // frames [f0, f0 + n) of the batch
     if (f >= n)
         return;
-    const uint64_t c = ck[f];
-    if (!(c >> 63) || uni((uint32_t)status[f]) != (uint32_t)ST_OK)
+    if (!(ck[f] >> 63) || uni((uint32_t)status[f]) != (uint32_t)ST_OK)
         return;
     const FrameDesc d = desc[f];
-    // (a no-cache read's last frame executed only up to the request's end:
-    // libzstd's streaming decoder never reaches the frame's end and its
-    // checksum there either)
-    if (f + 1 == n && stop_last < d.d_size)
-        return;
-    const uint32_t o0 = (uint32_t)(c >> 32) & 0x7FFFFFFFu, want = (uint32_t)c;
-    const uint8_t *p = out + d.d_off + o0;
-    const uint32_t len = d.d_size - o0;
-    const Span sp = make_span(p, len);
-    uint64_t acc = lane == 0 ? P64_1 + P64_2 : lane == 1 ? P64_2 : lane == 2 ? 0 : 0ull - P64_1;
-    const uint32_t stripes = len / 32;
-    for (uint32_t s0 = 0; s0 < stripes; s0 += 32) {
-        // 32 stripes = 1 KiB: 16 bytes per lane
-        const u32x4 v = load16u(sp.r, sp.s0 + 1024 * (s0 / 32) + 16 * lane);
-        *reinterpret_cast<u32x4 *>(&buf[w][2 * lane]) = v;
-        const uint32_t m = stripes - s0 < 32 ? stripes - s0 : 32;
-        if (lane < 4)
-            for (uint32_t i = 0; i < m; i++)
-                acc = xround(acc, buf[w][4 * i + lane]);
-    }
-    uint64_t h;
-    const uint64_t a1 = __shfl(acc, 1, 64), a2 = __shfl(acc, 2, 64), a3 = __shfl(acc, 3, 64);
-    if (len >= 32) {
-        h = rotl64(acc, 1) + rotl64(a1, 7) + rotl64(a2, 12) + rotl64(a3, 18);
-        h = xmerge(h, acc);
-        h = xmerge(h, a1);
-        h = xmerge(h, a2);
-        h = xmerge(h, a3);
-    } else {
-        h = P64_5;
-    }
-    h += len;
-    if (lane == 0) {
-        uint32_t i = stripes * 32;
-        for (; i + 8 <= len; i += 8) {
-            uint64_t k = 0;
-            for (int b = 0; b < 8; b++)
-                k |= (uint64_t)p[i + b] << (8 * b);
-            h ^= xround(0, k);
-            h = rotl64(h, 27) * P64_1 + P64_4;
+    // the entry's requests: its OP_FEND ops that the replay marked (a & 4)
+    // with the frame's start (e) and length (f), in order
+    const uint64_t ob = op_base(blk_base, f0 + f);
+    const uint32_t opn = (uint32_t)(op_base(blk_base, f0 + f + 1) - ob);
+    const ZOp *op = reinterpret_cast<const ZOp *>(ops) + ob;
+    for (uint32_t k = 0; k < opn; k++) {
+        const uint32_t kind = uni(op[k].k);
+        if (kind == OP_DONE || kind == OP_ERR)
+            break;
+        if (kind != OP_FEND || !(uni(op[k].a) & 4))
+            continue;
+        const uint32_t o0 = uni(op[k].e), len = uni(op[k].f), want = uni(op[k].d);
+        // (a no-cache read's last entry executed only up to the request's end:
+        // libzstd's streaming decoder never reaches this frame's end and its
+        // checksum there either, nor a later frame's)
+        if (f + 1 == n && stop_last < o0 + len)
+            break;
+        const uint8_t *p = out + d.d_off + o0;
+        uint32_t bad = 0;
+        const Span sp = make_span(p, len);
+        uint64_t acc = lane == 0 ? P64_1 + P64_2 : lane == 1 ? P64_2 : lane == 2 ? 0 : 0ull - P64_1;
+        const uint32_t stripes = len / 32;
+        for (uint32_t s0 = 0; s0 < stripes; s0 += 32) {
+            // 32 stripes = 1 KiB: 16 bytes per lane
+            const u32x4 v = load16u(sp.r, sp.s0 + 1024 * (s0 / 32) + 16 * lane);
+            *reinterpret_cast<u32x4 *>(&buf[w][2 * lane]) = v;
+            const uint32_t m = stripes - s0 < 32 ? stripes - s0 : 32;
+            if (lane < 4)
+                for (uint32_t i = 0; i < m; i++)
+                    acc = xround(acc, buf[w][4 * i + lane]);
         }
-        for (; i + 4 <= len; i += 4) {
-            const uint64_t k = (uint64_t)p[i] | (uint64_t)p[i + 1] << 8 | (uint64_t)p[i + 2] << 16 |
-                               (uint64_t)p[i + 3] << 24;
-            h ^= k * P64_1;
-            h = rotl64(h, 23) * P64_2 + P64_3;
+        uint64_t h;
+        const uint64_t a1 = __shfl(acc, 1, 64), a2 = __shfl(acc, 2, 64), a3 = __shfl(acc, 3, 64);
+        if (len >= 32) {
+            h = rotl64(acc, 1) + rotl64(a1, 7) + rotl64(a2, 12) + rotl64(a3, 18);
+            h = xmerge(h, acc);
+            h = xmerge(h, a1);
+            h = xmerge(h, a2);
+            h = xmerge(h, a3);
+        } else {
+            h = P64_5;
         }
-        for (; i < len; i++) {
-            h ^= p[i] * P64_5;
-            h = rotl64(h, 11) * P64_1;
+        h += len;
+        if (lane == 0) {
+            uint32_t i = stripes * 32;
+            for (; i + 8 <= len; i += 8) {
+                uint64_t k = 0;
+                for (int b = 0; b < 8; b++)
+                    k |= (uint64_t)p[i + b] << (8 * b);
+                h ^= xround(0, k);
+                h = rotl64(h, 27) * P64_1 + P64_4;
+            }
+            for (; i + 4 <= len; i += 4) {
+                const uint64_t k = (uint64_t)p[i] | (uint64_t)p[i + 1] << 8 | (uint64_t)p[i + 2] << 16 |
+                                   (uint64_t)p[i + 3] << 24;
+                h ^= k * P64_1;
+                h = rotl64(h, 23) * P64_2 + P64_3;
+            }
+            for (; i < len; i++) {
+                h ^= p[i] * P64_5;
+                h = rotl64(h, 11) * P64_1;
+            }
+            h ^= h >> 33;
+            h *= P64_2;
+            h ^= h >> 29;
+            h *= P64_3;
+            h ^= h >> 32;
+            bad = (uint32_t)h != want;
         }
-        h ^= h >> 33;
-        h *= P64_2;
-        h ^= h >> 29;
-        h *= P64_3;
-        h ^= h >> 32;
-        if ((uint32_t)h != want) {
-            status[f] = zerr(ZE_CHECKSUM);
-            if (fail_at)
-                fail_at[f] = d.d_size;   // checked at the frame's end
+        if (uni((uint32_t)__shfl((int)bad, 0, 64))) {
+            if (lane == 0) {
+                status[f] = zerr(ZE_CHECKSUM);
+                if (fail_at)
+                    fail_at[f] = o0 + len;   // checked at the frame's end
+            }
+            break;
         }
     }
 }
@@ -3589,7 +3620,8 @@ int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
         kernel_span_end(SPAN_ZEXEC, tx, stream);
         if (cks)   // (a host plan that met no content checksum: nothing to check)
             hipLaunchKernelGGL(zstd_check_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, d_desc + f0, m, d_out,
-                               s->ck + f0, d_status + f0, d_fail_at ? d_fail_at + f0 : nullptr, stop);
+                               s->ck + f0, s->ops, s->blk_base, d_status + f0,
+                               d_fail_at ? d_fail_at + f0 : nullptr, stop, f0);
     }
     stage_mark(3, stream);
     stage_mark(4, stream);

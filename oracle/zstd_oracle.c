@@ -257,6 +257,22 @@ static uint32_t bitd_look(const BitD *b, uint32_t nb)
     return (uint32_t)((b->c << (b->consumed & 63)) >> ((64 - nb) & 63));
 }
 
+/* BIT_readBitsFast (nb >= 1) */
+static uint64_t bitd_read_fast(BitD *b, uint32_t nb)
+{
+    const uint64_t v = bitd_look(b, nb);
+    b->consumed += nb;
+    return v;
+}
+
+/* BIT_readBits: BIT_lookBits is BIT_getMiddleBits(container, 64 - consumed - nb, nb) */
+static uint64_t bitd_read(BitD *b, uint32_t nb)
+{
+    const uint64_t v = (b->c >> ((64u - b->consumed - nb) & 63)) & ((1ull << nb) - 1);
+    b->consumed += nb;
+    return v;
+}
+
 /* BIT_reloadDStream */
 static int bitd_reload(BitD *b)
 {
@@ -865,6 +881,10 @@ static int block(Dec *D, const uint8_t *p, size_t n, uint8_t *out, size_t cap, s
     if (q >= qe)
         return -ZE_SRC_WRONG;
     uint32_t nseq = q[0];
+    /* a count of 0 in a 2- or 3-byte form still has its mode byte and table
+     * descriptions read (ZSTD_decodeSeqHeaders returns early on a first byte
+     * of 0 only); what follows them is not looked at */
+    const int tables = nseq != 0;
     if (nseq == 0) {
         if (qe - q != 1)
             return -ZE_SRC_WRONG;
@@ -884,7 +904,7 @@ static int block(Dec *D, const uint8_t *p, size_t n, uint8_t *out, size_t cap, s
     }
     size_t o = *op;
     const uint8_t *lp = D->lit, *le = D->lit + litn;
-    if (nseq) {
+    if (tables) {
         if (q + 1 > qe)
             return -ZE_SRC_WRONG;
         const uint32_t modes = *q++;
@@ -900,19 +920,37 @@ static int block(Dec *D, const uint8_t *p, size_t n, uint8_t *out, size_t cap, s
         if (r < 0)
             return (int)r;
         q += r;
-        BitR b;
-        if (bitr_init(&b, q, (size_t)(qe - q)) != 0)
+    }
+    if (nseq) {
+        /* The bit reads are libzstd 1.4.9's on its 64-bit container, reload
+         * for reload (ZSTD_decompressSequences_body, ZSTD_decodeSequence on a
+         * 64-bit host): its loop decodes every counted sequence and never
+         * looks at a reload's result, so a stream that is too short is read
+         * on past its start -- where the shifts wrap inside the container
+         * (BIT_lookBitsFast shifts by bitsConsumed & 63, BIT_lookBits takes
+         * the middle bits at (64 - bitsConsumed - n) & 63) instead of giving
+         * zeros -- and only what those bits decode to, or bits left over at
+         * the end, fails the block. */
+        BitD b;
+        if (bitd_init(&b, q, (size_t)(qe - q)) != 0)
             return -ZE_CORRUPTION;
-        uint32_t sll = (uint32_t)bitr_read(&b, D->ll.log);
-        uint32_t sof = (uint32_t)bitr_read(&b, D->of.log);
-        uint32_t sml = (uint32_t)bitr_read(&b, D->ml.log);
+        uint32_t sll = (uint32_t)bitd_read(&b, (uint32_t)D->ll.log);
+        bitd_reload(&b);
+        uint32_t sof = (uint32_t)bitd_read(&b, (uint32_t)D->of.log);
+        bitd_reload(&b);
+        uint32_t sml = (uint32_t)bitd_read(&b, (uint32_t)D->ml.log);
+        bitd_reload(&b);
         for (uint32_t i = 0; i < nseq; i++) {
+            if (i)
+                bitd_reload(&b);
             const uint32_t llc = D->ll.t[sll].sym, ofc = D->of.t[sof].sym, mlc = D->ml.t[sml].sym;
             if (llc > 35 || mlc > 52 || ofc > 31)
                 return -ZE_CORRUPTION;
-            uint64_t ofv = (1ull << ofc) + bitr_read(&b, ofc);
-            const uint32_t ml = ML_BASE[mlc] + (uint32_t)bitr_read(&b, ML_BITS[mlc]);
-            const uint32_t ll = LL_BASE[llc] + (uint32_t)bitr_read(&b, LL_BITS[llc]);
+            uint64_t ofv = (1ull << ofc) + (ofc ? bitd_read_fast(&b, ofc) : 0);
+            const uint32_t ml = ML_BASE[mlc] + (ML_BITS[mlc] ? (uint32_t)bitd_read_fast(&b, ML_BITS[mlc]) : 0);
+            if (ofc + ML_BITS[mlc] + LL_BITS[llc] >= 57 - (9 + 9 + 8))
+                bitd_reload(&b);
+            const uint32_t ll = LL_BASE[llc] + (LL_BITS[llc] ? (uint32_t)bitd_read_fast(&b, LL_BITS[llc]) : 0);
             uint64_t off;
             if (ofv > 3) {
                 off = ofv - 3;
@@ -933,9 +971,9 @@ static int block(Dec *D, const uint8_t *p, size_t n, uint8_t *out, size_t cap, s
                     D->rep[0] = (uint32_t)off;
                 }
             }
-            sll = D->ll.t[sll].base + (uint32_t)bitr_read(&b, D->ll.t[sll].nb);
-            sml = D->ml.t[sml].base + (uint32_t)bitr_read(&b, D->ml.t[sml].nb);
-            sof = D->of.t[sof].base + (uint32_t)bitr_read(&b, D->of.t[sof].nb);
+            sll = D->ll.t[sll].base + (uint32_t)bitd_read(&b, D->ll.t[sll].nb);
+            sml = D->ml.t[sml].base + (uint32_t)bitd_read(&b, D->ml.t[sml].nb);
+            sof = D->of.t[sof].base + (uint32_t)bitd_read(&b, D->of.t[sof].nb);
             /* execute */
             if ((uint64_t)o + ll + ml > cap)
                 return -ZE_DST_TOO_SMALL;
@@ -950,7 +988,7 @@ static int block(Dec *D, const uint8_t *p, size_t n, uint8_t *out, size_t cap, s
                 out[o + k] = out[o + k - off];
             o += ml;
         }
-        if (b.pos > 0)
+        if (bitd_reload(&b) < BD_COMPLETED)   /* bits left over */
             return -ZE_CORRUPTION;
     }
     const size_t last = (size_t)(le - lp);
