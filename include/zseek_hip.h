@@ -577,6 +577,52 @@ ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *d_desc,
     void *d_scratch, size_t scratch_size, void *stream);
 
 /*
+ * The same call with the format as an argument.  ZSK_ZSTD_FORMAT_SUBSET is
+ * zsk_zstd_compress_frames, byte for byte.  ZSK_ZSTD_FORMAT_FULL
+ * (csrc/zstd_enc_full_dev.h) keeps the subset's frame header, 128 KiB blocks,
+ * block-type rule (Compressed only when smaller than the block's input),
+ * stream count and match search, and changes four things:
+ *   literals  Huffman over all 256 byte values (code lengths <= 11).  The tree
+ *             is described by direct 4-bit weights (legal when at most 128 are
+ *             listed) or by FSE-compressed weights (header byte < 128,
+ *             accuracy log <= 6, two interleaved states), whichever is
+ *             smaller, direct on a tie.  Where neither is legal (all listed
+ *             weights equal; 128 bytes or more) or Huffman is not smaller, the
+ *             literals are Raw, or RLE for one repeated byte.
+ *   tables    LL, OF and ML are each Predefined, RLE (every sequence of the
+ *             block has the same code) or FSE_Compressed, per block.  A block
+ *             of fewer than 8 sequences uses the predefined tables.  Otherwise
+ *             the accuracy log is highbit(nseq - 1) - 2, at least
+ *             min(highbit(nseq) + 1, highbit(largest code) + 2) and 5, at most
+ *             9 (LL, ML) or 8 (OF); a count below one table cell is "less than
+ *             one", the others round half up, the difference to the table
+ *             size goes to (or comes one at a time from) the largest share;
+ *             and the mode with the lowest cost in 1/256 bit wins, Predefined
+ *             on a tie: description bits + accuracy log + per sequence
+ *             (accuracy log - log2 of the code's share) in 8-bit fixed point.
+ *   offsets   repeat codes: an offset equal to one of the three last offsets
+ *             is coded 1..3 by RFC 8878 3.1.1.5 (without literals before the
+ *             match: the second, the third, the first minus one; the first
+ *             itself is then coded plain).  The history starts at 1, 4, 8 in
+ *             every frame, passes from block to block, and only a block that
+ *             is written Compressed moves it on.
+ * Still not written: matches into earlier blocks, Repeat_Mode or treeless
+ * tables, dictionaries, frames above ZSK_ZSTD_COMPRESS_MAX_FRAME, levels.
+ * The contract is zsk_zstd_compress_frames' whole: asynchronous on @stream,
+ * one compress kernel per call, the same slots and bound, nothing written
+ * outside them, no source byte read outside the frame, a frame above the cap
+ * refused with c_size 0 and its slot untouched, the same bytes on every run,
+ * ZSK_COMPRESS_CONTENT_CHECKSUM honoured.  An unknown @format returns -1 (0
+ * from the scratch size) and queues nothing.
+ */
+#define ZSK_ZSTD_FORMAT_SUBSET 0   /* zsk_zstd_compress_frames' frames, byte for byte */
+#define ZSK_ZSTD_FORMAT_FULL   1
+ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size_ex(uint32_t nframes, uint64_t src_bytes, int format);
+ZSEEK_EXPORT int zsk_zstd_compress_frames_ex(const zsk_compress_desc_t *d_desc,
+    uint32_t nframes, const void *d_src, void *d_dst, uint32_t *d_csize,
+    void *d_scratch, size_t scratch_size, void *stream, int format);
+
+/*
  * Writer GPU mode: an LZ4 writer's frames of <= 4 MiB are compressed on the
  * GPU (zsk_lz4_compress_frames, on the calling thread's current device) in
  * batches of @batch_bytes input bytes (0: 1 GiB; (size_t)-1: GPU mode off,
@@ -733,7 +779,9 @@ ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t f
  * ZSK_ZSTD_COMPRESS_MAX_FRAME), the last one the rest; len == 0 gives the
  * empty table alone.  ZSK_IMAGE_CHECKSUMS: 12-byte table entries;
  * ZSK_IMAGE_CONTENT_CHECKSUMS: the same XXH64 word (computed once) also ends
- * each frame.  @batch_bytes 0: 256 MiB.  zsk_zstd_image_bound: every frame at
+ * each frame.  ZSK_IMAGE_ZSTD_FULL: the frames in ZSK_ZSTD_FORMAT_FULL (the
+ * bounds and the scratch are the same; zsk_lz4_build_image ignores the bit).
+ * @batch_bytes 0: 256 MiB.  zsk_zstd_image_bound: every frame at
  * its bound plus the table; 0 for frame_size == 0.  Errors are
  * zsk_lz4_build_image's, under the same conditions (there is no level).  The
  * result is read as zstd by the reference reader and zsk_reader_open_device.
@@ -741,6 +789,7 @@ ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t f
  * place of the LZ4 tables: 512 KiB per frame of a batch, at most 896 MiB.
  */
 #define ZSK_IMAGE_CONTENT_CHECKSUMS 2u
+#define ZSK_IMAGE_ZSTD_FULL 4u     /* zsk_zstd_build_image: frames in the full format */
 ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_size, unsigned flags);
 ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size,
     unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,

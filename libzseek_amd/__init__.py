@@ -12,5 +12,5 @@ from .zseek import (  # noqa: F401
     synth_buffer, tools, verify_frame_checksums, with_frame_checksums, zstd_decode_frames,
     zstd_seekable, zstd_tool_version, lz4_image_bound, lz4_build_image,
     zstd_compress_bound, zstd_compress_layout, zstd_compress_scratch_size, zstd_compress_frames,
-    zstd_image_bound, zstd_build_image,
+    zstd_image_bound, zstd_build_image, ZSTD_FORMAT_SUBSET, ZSTD_FORMAT_FULL, IMAGE_ZSTD_FULL,
 )

@@ -193,13 +193,16 @@ bool grow(uint8_t **p, size_t *cap, size_t want)
 struct Codec {
     bool zstd;
     uint64_t max_frame;
+    int format;   // zstd: ZSK_ZSTD_FORMAT_*
     uint64_t bound(uint64_t n) const { return zstd ? ZSK_ZSTD_COMPRESS_BOUND(n) : ZSK_LZ4_COMPRESS_BOUND(n); }
     size_t scratch(uint32_t nframes) const
     {
         return zstd ? zstd_compress_scratch_size(nframes) : zsk_lz4_compress_scratch_size(nframes);
     }
 };
-constexpr Codec kLz4{false, ZSK_LZ4_COMPRESS_MAX_FRAME}, kZstd{true, ZSK_ZSTD_COMPRESS_MAX_FRAME};
+constexpr Codec kLz4{false, ZSK_LZ4_COMPRESS_MAX_FRAME, 0},
+    kZstd{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_SUBSET},
+    kZstdFull{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_FULL};
 
 struct Geometry {
     uint64_t frames, full, tail, entry, bound;
@@ -343,7 +346,7 @@ ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t fr
                            f * (uint64_t)frame_size, (uint64_t)frame_size, (uint64_t)len, slot, cflags, tail_flags);
         ok = hipGetLastError() == hipSuccess && (!ck || launch_src_checksums(d_cdesc, n, src, d_sums, stream) == 0) &&
              (codec.zstd ? launch_zstd_compress(d_cdesc, n, src, s->slots, d_csize, s->tables, s->tables_cap,
-                                                in_frame ? d_sums : nullptr, stream)
+                                                in_frame ? d_sums : nullptr, stream, codec.format)
                          : zsk_lz4_compress_frames(d_cdesc, n, src, s->slots, d_csize, level, s->tables, stream)) == 0;
         if (!ok)
             break;
@@ -403,5 +406,6 @@ extern "C" ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_siz
 extern "C" ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size, unsigned flags,
                                                      size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
 {
-    return build_image(kZstd, d_src, len, frame_size, 0, flags, batch_bytes, d_image, capacity, errbuf);
+    return build_image((flags & ZSK_IMAGE_ZSTD_FULL) ? kZstdFull : kZstd, d_src, len, frame_size, 0, flags, batch_bytes,
+                       d_image, capacity, errbuf);
 }

@@ -510,11 +510,12 @@ int launch_src_checksums(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
 // zstd frame compression (zstd_compress.hip; zsk_zstd_compress_frames'
 // contract).  d_sums: the frames' XXH64 low words when the caller already has
 // them (the image builder), nullptr to compute those the descriptors ask for
-// into the scratch.  Asynchronous on stream; 0 or -1.
+// into the scratch.  format: ZSK_ZSTD_FORMAT_* (an unknown one: -1); the
+// scratch is the same for both.  Asynchronous on stream; 0 or -1.
 size_t zstd_compress_scratch_size(uint32_t nframes);
 int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst,
                          uint32_t *d_csize, void *d_scratch, size_t scratch_size, const uint32_t *d_sums,
-                         hipStream_t stream);
+                         hipStream_t stream, int format);
 
 // A reader over a seekable file in device memory (image_build.hip,
 // image_desc_kernel): the descriptors of the n frames from f0 on, written on

@@ -1,11 +1,17 @@
 // zstd_compress.hip — zstd frame compression on the GPU (gfx950):
-// zsk_zstd_compress_frames.  The frames are valid zstd (RFC 8878) that libzstd
-// decodes to the input; they are not libzstd's bytes at any level, and there
-// is one effort level.  The format subset and everything that decides bytes
-// once the matches are known is zstd_enc_dev.h (shared with the CPU shim of
-// tests/test_zstd_enc.py); what it leaves out -- FSE-compressed Huffman
-// weights (so literals holding a byte above 128 are stored Raw), repeat
-// offsets, custom or repeated tables, frames above 4 MiB -- is listed there.
+// zsk_zstd_compress_frames and zsk_zstd_compress_frames_ex.  The frames are
+// valid zstd (RFC 8878) that libzstd decodes to the input; they are not
+// libzstd's bytes at any level, and there is one effort level.  Two formats,
+// one kernel instantiation each, one launch per call:
+//   subset  zstd_enc_dev.h (shared with the CPU shim of tests/test_zstd_enc.py):
+//           everything that decides bytes once the matches are known.  It
+//           leaves out FSE-compressed Huffman weights (so literals holding a
+//           byte above 128 are stored Raw), repeat offsets, custom or repeated
+//           tables, frames above 4 MiB.
+//   full    zstd_enc_full_dev.h (tests/test_zstd_enc_full.py's shim): Huffman
+//           over all 256 byte values with the smaller of the two tree
+//           descriptions, a mode per sequence table and block, repeat offsets.
+//           Same match search, so the same sequences; see "full" below.
 //
 // Mapping: one single-wave workgroup per frame, the frame's blocks (kZBlock
 // input bytes each) in order, each block independent of the others: a fresh
@@ -27,6 +33,18 @@
 //              tables, which the workgroup builds in LDS once
 //   assemble   the block is written where it lands: a block's size is known
 //              before the next one starts, so no scan is needed
+//   full       after the match search the hash table is dead and the block's
+//              work lies over it (PostF).  The offsets become offset values
+//              in sequence order (each depends on the history): the wave
+//              loads 64 sequences and walks them as one (wave_offsets); it
+//              counts the three code histograms by LDS atomics and ranks the
+//              256 literal counts (every lane four symbols: the sort of
+//              huf_lengths without its quadratic walk on one lane); one lane
+//              builds lengths, the tree description, and -- bounded by the
+//              alphabets -- normalises, describes and builds the tables it
+//              chooses; bit sums, literal copy and the four streams are the
+//              subset's.  The frame's offset history sits in LDS and moves on
+//              only when a block is written Compressed.
 // Source bytes are read only inside the frame (a 4-byte read always lies
 // within it); nothing is written outside the slot's ZSK_ZSTD_COMPRESS_BOUND.
 //
@@ -36,10 +54,12 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/zseek_hip.h"
 #include "zsk_internal.h"
 #include "zstd_enc_dev.h"
+#include "zstd_enc_full_dev.h"
 
 namespace zsk {
 
@@ -57,6 +77,7 @@ constexpr uint32_t kGridMax = 1792;                   // workgroups that walk a 
 constexpr uint32_t kSeqMax = kZBlock / kMinMatch;     // sequences a block can hold
 constexpr size_t kWgScratch = kZBlock + (size_t)kSeqMax * sizeof(Seq);
 
+// The subset kernel's LDS.
 struct Lds {
     uint32_t tab[1u << kHashLog];    // position + 1 by hash; 0: empty
     uint32_t count[kHufSyms + 1];    // literal histogram; [kHufSyms]: bytes above 128
@@ -68,13 +89,45 @@ struct Lds {
     uint32_t wants, comp;
 };
 
+// The full kernel's LDS.  Everything a block needs once its matches are found
+// lies over the hash table, which is dead by then; within that, the Huffman
+// work area and the custom FSE tables, which are not live together, share
+// their bytes.  What the match search fills (count) or a frame keeps (T, rep)
+// stays outside.
+struct PostF {
+    union {
+        uint32_t ws[kHufWorkWordsF];   // huf_lengths_sorted's
+        SeqWork W;                     // seq_plan's: the custom tables
+    };
+    HufCodeF huf;
+    FseCT wt;                          // the weights' table
+    uint32_t hist[3][64];              // LL, OF, ML code histograms
+    SeqPlan seq;
+    uint8_t hdesc[kHufDescMax];        // the tree description
+    uint32_t hdesc_len;
+};
+
+struct LdsF {
+    union {
+        uint32_t tab[1u << kHashLog];
+        PostF post;
+    };
+    uint32_t count[kHufSymsF];
+    uint32_t bits[4];
+    SeqTables T;                       // the predefined tables
+    LitPlan plan;
+    Reps rep, next;                    // the frame's offset history; after this block
+    uint32_t wants, comp;
+};
+static_assert(sizeof(PostF) <= sizeof(uint32_t) << kHashLog, "the block's work fits in the dead hash table");
+
 __device__ __forceinline__ uint32_t ld4(const uint8_t *p)
 {
     return *reinterpret_cast<const u32_ua *>(p);
 }
 
 // in[0..n) is one repeated byte (n >= 1).
-__device__ bool one_byte_run(const uint8_t *in, uint32_t n)
+__device__ __forceinline__ bool one_byte_run(const uint8_t *in, uint32_t n)
 {
     const uint32_t lane = threadIdx.x;
     const uint8_t b = in[0];
@@ -86,45 +139,28 @@ __device__ bool one_byte_run(const uint8_t *in, uint32_t n)
     return true;
 }
 
-// Literals s[from, from + len) behind lit[nlit), counted.
-__device__ __forceinline__ void take_literals(Lds &L, const uint8_t *s, uint32_t from, uint32_t len, uint8_t *lit,
-                                              uint32_t nlit)
+// Literals s[from, from + len) behind lit[nlit), counted: the subset in bins
+// 0..128 and one for the bytes above, the full format in 256.
+template <bool kFull>
+__device__ __forceinline__ void take_literals(uint32_t *count, const uint8_t *s, uint32_t from, uint32_t len,
+                                              uint8_t *lit, uint32_t nlit)
 {
     for (uint32_t i = threadIdx.x; i < len; i += 64) {
         const uint32_t c = s[from + i];
         lit[nlit + i] = (uint8_t)c;
-        atomicAdd(&L.count[c < kHufSyms ? c : kHufSyms], 1u);
+        atomicAdd(&count[kFull || c < kHufSyms ? c : kHufSyms], 1u);
     }
 }
 
-// Block s[b0, b0 + bn) of the frame s at dst; returns its size with the
-// 3-byte header.  Wave-uniform: every lane takes every branch together.
-__device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32_t b0, uint32_t bn, bool last,
-                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq)
+// The match search of block s[b0, b0 + bn) (the file's head): the literals
+// compacted into lit and counted, the sequences into seq.  tab and count are
+// cleared by the caller; wave-uniform, and ends on a barrier.
+template <bool kFull>
+__device__ __forceinline__ void find_matches(uint32_t *tab, uint32_t *count, const uint8_t *__restrict__ s,
+                                             uint32_t b0, uint32_t bn, uint8_t *__restrict__ lit,
+                                             Seq *__restrict__ seq, uint32_t &nseq_out, uint32_t &nlit_out)
 {
-    const uint32_t lane = threadIdx.x;
-    if (bn == 0) {
-        if (lane == 0)
-            block_header(dst, last, kBlockRaw, 0);
-        return 3;
-    }
-    if (one_byte_run(s + b0, bn)) {
-        if (lane == 0) {
-            block_header(dst, last, block_choice(bn, true, 0), bn);
-            dst[3] = s[b0];
-        }
-        return 4;
-    }
-    for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
-        L.tab[i] = 0;
-    for (uint32_t i = lane; i < kHufSyms + 1; i += 64)
-        L.count[i] = 0;
-    if (lane < 4)
-        L.bits[lane] = 0;
-    __syncthreads();
-
-    // ---- match
-    const uint32_t end = b0 + bn;
+    const uint32_t lane = threadIdx.x, end = b0 + bn;
     uint32_t anchor = b0, base = b0, nseq = 0, nlit = 0;
     while (base + kMinMatch <= end) {
         const uint32_t pos = base + lane;
@@ -133,13 +169,13 @@ __device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32
         if (valid) {
             v = ld4(s + pos);
             h = match_hash(v);
-            cand = L.tab[h];
+            cand = tab[h];
         }
         const bool hit = valid && cand != 0 && ld4(s + cand - 1) == v;
         const uint64_t hits = __ballot(hit);
         if (hits == 0) {
             if (valid)
-                atomicMax(&L.tab[h], pos + 1);
+                atomicMax(&tab[h], pos + 1);
             __syncthreads();
             base += 64;
             continue;
@@ -167,9 +203,9 @@ __device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32
         }
         const uint32_t next = mpos + ml;
         if (valid && pos < next)
-            atomicMax(&L.tab[h], pos + 1);
+            atomicMax(&tab[h], pos + 1);
         const uint32_t ll = mpos - anchor;
-        take_literals(L, s, anchor, ll, lit, nlit);
+        take_literals<kFull>(count, s, anchor, ll, lit, nlit);
         if (lane == 0)
             seq[nseq] = Seq{ll, ml, mpos - mc};
         nseq++;
@@ -177,10 +213,40 @@ __device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32
         anchor = base = next;
         __syncthreads();
     }
-    take_literals(L, s, anchor, end - anchor, lit, nlit);
+    take_literals<kFull>(count, s, anchor, end - anchor, lit, nlit);
     nlit += end - anchor;
     __syncthreads();
+    nseq_out = nseq;
+    nlit_out = nlit;
+}
 
+// Block s[b0, b0 + bn) of the frame s at dst; returns its size with the
+// 3-byte header.  Wave-uniform: every lane takes every branch together.
+__device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32_t b0, uint32_t bn, bool last,
+                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq)
+{
+    const uint32_t lane = threadIdx.x;
+    if (bn == 0) {
+        if (lane == 0)
+            block_header(dst, last, kBlockRaw, 0);
+        return 3;
+    }
+    if (one_byte_run(s + b0, bn)) {
+        if (lane == 0) {
+            block_header(dst, last, block_choice(bn, true, 0), bn);
+            dst[3] = s[b0];
+        }
+        return 4;
+    }
+    for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
+        L.tab[i] = 0;
+    for (uint32_t i = lane; i < kHufSyms + 1; i += 64)
+        L.count[i] = 0;
+    if (lane < 4)
+        L.bits[lane] = 0;
+    __syncthreads();
+    uint32_t nseq, nlit;   // ---- match
+    find_matches<false>(L.tab, L.count, s, b0, bn, lit, seq, nseq, nlit);
     // ---- literals: the plan
     if (lane == 0)
         L.wants = lit_wants_huf(L.count, L.count[kHufSyms], nlit, L.huf, L.ws, L.plan) ? 1u : 0u;
@@ -244,16 +310,176 @@ __device__ uint32_t compress_block(Lds &L, const uint8_t *__restrict__ s, uint32
     return 3 + bn;
 }
 
+// seq_offsets by the whole wave: sequences are taken 64 at a time, a lane
+// each; every lane then walks the same history through the batch in order
+// (sequence j's ll and off read from lane j: wave-uniform values, so the walk
+// is scalar work) and keeps the value of its own sequence.  The serial order
+// without a memory round trip per step.  Returns the history after the block.
+__device__ __forceinline__ Reps wave_offsets(Reps h, Seq *__restrict__ seq, uint32_t nseq)
+{
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t base = 0; base < nseq; base += 64) {
+        const uint32_t i = base + lane, cnt = min(64u, nseq - base);
+        uint32_t ll = 0, off = 0, mine = 0;
+        if (i < nseq) {
+            ll = seq[i].ll;
+            off = seq[i].off;
+        }
+        for (uint32_t j = 0; j < cnt; j++) {
+            const uint32_t v = rep_code(h, (uint32_t)__builtin_amdgcn_readlane((int)ll, (int)j),
+                                        (uint32_t)__builtin_amdgcn_readlane((int)off, (int)j));
+            if (lane == j)
+                mine = v;
+        }
+        if (i < nseq)
+            seq[i].off = mine;
+    }
+    return h;
+}
+
+// ... in the full format (zstd_enc_full_dev.h).  L.rep is the frame's offset
+// history before the block; a block written Compressed moves it on.  Kept out
+// of line: inlined into the frame loop it takes more than 256 VGPRs (hundreds
+// of SGPRs spilled into them); as a function it takes 84.
+__device__ __noinline__ uint32_t compress_block(LdsF &L, const uint8_t *__restrict__ s, uint32_t b0, uint32_t bn, bool last,
+                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq)
+{
+    const uint32_t lane = threadIdx.x;
+    if (bn == 0) {
+        if (lane == 0)
+            block_header(dst, last, kBlockRaw, 0);
+        return 3;
+    }
+    if (one_byte_run(s + b0, bn)) {
+        if (lane == 0) {
+            block_header(dst, last, block_choice(bn, true, 0), bn);
+            dst[3] = s[b0];
+        }
+        return 4;
+    }
+    for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
+        L.tab[i] = 0;
+    for (uint32_t i = lane; i < kHufSymsF; i += 64)
+        L.count[i] = 0;
+    if (lane < 4)
+        L.bits[lane] = 0;
+    __syncthreads();
+    uint32_t nseq, nlit;   // ---- match
+    find_matches<true>(L.tab, L.count, s, b0, bn, lit, seq, nseq, nlit);
+    PostF &P = L.post;     // (the hash table is dead from here)
+
+    // ---- offsets into offset values: serial in the history
+    for (uint32_t i = lane; i < 3 * 64; i += 64)
+        (&P.hist[0][0])[i] = 0;
+    const Reps next = wave_offsets(L.rep, seq, nseq);
+    if (lane == 0) {
+        L.next = next;
+        L.wants = lit_wants_huf_f(L.count, nlit, L.plan) ? 1u : 0u;
+    }
+    __syncthreads();
+    const bool tries = L.wants != 0;
+    // ---- the three code histograms
+    for (uint32_t i = lane; i < nseq; i += 64) {
+        const Seq q = seq[i];
+        atomicAdd(&P.hist[0][ll_code(q.ll)], 1u);
+        atomicAdd(&P.hist[1][highbit(q.off)], 1u);
+        atomicAdd(&P.hist[2][ml_code(q.ml)], 1u);
+    }
+    // ---- literals: the sort by the wave, lengths and description by one lane
+    if (tries) {
+        uint8_t *const order = huf_order(P.ws);
+        for (uint32_t c = lane; c < kHufSymsF; c += 64)
+            if (L.count[c] != 0)
+                order[huf_rank(L.count, c)] = (uint8_t)c;
+    }
+    __syncthreads();
+    if (tries) {
+        if (lane == 0) {
+            huf_lengths_sorted(L.count, P.huf, P.ws);
+            P.hdesc_len = P.huf.max_bits ? huf_desc_f(P.huf, P.wt, P.hdesc) : 0;
+            L.wants = P.hdesc_len != 0 ? 1u : 0u;
+        }
+        __syncthreads();
+    }
+    const uint32_t ns = huf_streams(nlit), seg = huf_segment(nlit);
+    if (tries && L.wants) {   // (0 now: no legal description)
+        for (uint32_t k = 0; k < ns; k++) {
+            const uint32_t a = ns == 4 ? k * seg : 0, b = ns == 4 && k < 3 ? a + seg : nlit;
+            uint32_t sum = 0;
+            for (uint32_t i = a + lane; i < b; i += 64)
+                sum += P.huf.len[lit[i]];
+            atomicAdd(&L.bits[k], sum);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            const uint64_t bits[4] = {L.bits[0], L.bits[1], L.bits[2], L.bits[3]};
+            lit_plan_huf_f(P.hdesc_len, bits, L.plan);
+        }
+        __syncthreads();
+    }
+    const uint32_t mode = L.plan.mode, lsize = L.plan.size;
+    if (lane == 0)
+        L.comp = 0;
+    uint8_t *const body = dst + 3;
+    if (lsize + 1 < bn) {
+        // ---- literals and sequences, where they land
+        if (lane == 0)
+            lit_write_head_f(L.plan, P.hdesc, P.hdesc_len, body);
+        if (mode == kLitRaw) {
+            const uint32_t head = lsize - nlit;
+            for (uint32_t i = lane; i < nlit; i += 64)
+                body[head + i] = lit[i];
+        } else if (mode == kLitRle) {
+            if (lane == 0)
+                body[lsize - 1] = lit[0];
+        } else if (lane < ns) {
+            uint32_t off = lsize;   // the streams end the section
+            for (uint32_t k = lane; k < ns; k++)
+                off -= L.plan.stream[k];
+            const uint32_t a = ns == 4 ? lane * seg : 0, b = ns == 4 && lane < 3 ? a + seg : nlit;
+            huf_encode_stream_f(P.huf, lit + a, b - a, body + off, body + off + L.plan.stream[lane]);
+        }
+        if (lane == 0) {
+            seq_plan(P.hist, nseq, L.T, P.W, P.seq);   // (the Huffman work area is dead)
+            const uint32_t sz = seq_section_f(P.seq, seq, nseq, body + lsize, body + bn);
+            L.comp = sz ? lsize + sz : 0;
+        }
+    }
+    __syncthreads();
+    const uint32_t comp = L.comp;
+    const uint32_t type = block_choice(bn, false, comp);
+    __syncthreads();   // (L.comp is rewritten by the next block)
+    if (type == kBlockCompressed) {
+        if (lane == 0) {
+            block_header(dst, last, type, comp);
+            L.rep = L.next;
+        }
+        return 3 + comp;
+    }
+    if (lane == 0)
+        block_header(dst, last, kBlockRaw, bn);
+    for (uint32_t i = lane; i < bn; i += 64)
+        body[i] = s[b0 + i];
+    return 3 + bn;
+}
+
+// One instantiation per format: the subset's is the kernel it was before the
+// full format existed, with its LDS, registers and seven workgroups per CU.
+template <bool kFull>
 __global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_desc_t *__restrict__ desc,
                                                            uint32_t nframes, const uint8_t *__restrict__ src,
                                                            uint8_t *__restrict__ dst, uint32_t *__restrict__ csize,
                                                            const uint32_t *__restrict__ sums,
                                                            uint8_t *__restrict__ scratch)
 {
-    __shared__ Lds L;
+    __shared__ typename std::conditional<kFull, LdsF, Lds>::type L;
     const uint32_t lane = threadIdx.x;
-    if (lane == 0)
-        seq_tables_build(L.T);
+    if (lane == 0) {
+        if constexpr (kFull)
+            seq_tables_build_f(L.T);
+        else
+            seq_tables_build(L.T);
+    }
     __syncthreads();
     uint8_t *const lit = scratch + (size_t)blockIdx.x * kWgScratch;
     Seq *const seq = reinterpret_cast<Seq *>(lit + kZBlock);
@@ -270,6 +496,10 @@ __global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_de
         const bool ck = (d.flags & ZSK_COMPRESS_CONTENT_CHECKSUM) != 0;
         if (lane == 0)
             frame_header(out, n, ck);
+        if constexpr (kFull) {
+            if (lane == 0)
+                reps_init(L.rep);
+        }
         uint32_t at = frame_header_size(n);
         const uint32_t nb = frame_blocks(n);
         for (uint32_t b = 0; b < nb; b++) {
@@ -312,6 +542,12 @@ uint32_t grid_of(uint32_t nframes)
 
 }   // namespace
 
+bool zstd_format_known(int format)
+{
+    return format == ZSK_ZSTD_FORMAT_SUBSET || format == ZSK_ZSTD_FORMAT_FULL;
+}
+
+// (the same for both formats: what the full one adds lives in LDS)
 size_t zstd_compress_scratch_size(uint32_t nframes)
 {
     if (nframes == 0)
@@ -322,8 +558,10 @@ size_t zstd_compress_scratch_size(uint32_t nframes)
 
 int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst,
                          uint32_t *d_csize, void *d_scratch, size_t scratch_size, const uint32_t *d_sums,
-                         hipStream_t stream)
+                         hipStream_t stream, int format)
 {
+    if (!zstd_format_known(format))
+        return -1;
     if (nframes == 0)
         return 0;
     if (!d_desc || !d_src || !d_dst || !d_csize || !d_scratch || scratch_size < zstd_compress_scratch_size(nframes))
@@ -340,8 +578,12 @@ int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
             return -1;
         d_sums = sums;
     }
-    hipLaunchKernelGGL(zstd_compress_kernel, dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src, d_dst, d_csize,
-                       d_sums, wg);
+    if (format == ZSK_ZSTD_FORMAT_FULL)
+        hipLaunchKernelGGL(zstd_compress_kernel<true>, dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src, d_dst,
+                           d_csize, d_sums, wg);
+    else
+        hipLaunchKernelGGL(zstd_compress_kernel<false>, dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src, d_dst,
+                           d_csize, d_sums, wg);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -359,5 +601,21 @@ extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *
 {
     return zsk::launch_zstd_compress(d_desc, nframes, static_cast<const uint8_t *>(d_src),
                                      static_cast<uint8_t *>(d_dst), d_csize, d_scratch, scratch_size, nullptr,
-                                     static_cast<hipStream_t>(stream));
+                                     static_cast<hipStream_t>(stream), ZSK_ZSTD_FORMAT_SUBSET);
+}
+
+extern "C" ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size_ex(uint32_t nframes, uint64_t src_bytes, int format)
+{
+    (void)src_bytes;
+    return zsk::zstd_format_known(format) ? zsk::zstd_compress_scratch_size(nframes) : 0;
+}
+
+extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames_ex(const zsk_compress_desc_t *d_desc, uint32_t nframes,
+                                                        const void *d_src, void *d_dst, uint32_t *d_csize,
+                                                        void *d_scratch, size_t scratch_size, void *stream,
+                                                        int format)
+{
+    return zsk::launch_zstd_compress(d_desc, nframes, static_cast<const uint8_t *>(d_src),
+                                     static_cast<uint8_t *>(d_dst), d_csize, d_scratch, scratch_size, nullptr,
+                                     static_cast<hipStream_t>(stream), format);
 }

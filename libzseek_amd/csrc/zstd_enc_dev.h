@@ -21,6 +21,12 @@
 //             coded as offset + 3 (no repeat codes), one backward bitstream
 // Not written: repeat or treeless tables, custom FSE tables, repeat offsets,
 // dictionaries, windows (frames are single-segment, <= 4 MiB).
+//
+// This file is ZSK_ZSTD_FORMAT_SUBSET and stays as it is: its frames are pinned
+// byte for byte (tests/golden/zstd_enc_subset.json).  ZSK_ZSTD_FORMAT_FULL --
+// Huffman over all 256 byte values with FSE-compressed weights, a mode per
+// sequence table, repeat offsets -- is zstd_enc_full_dev.h, which adds its
+// layer beside these functions and uses them.
 #pragma once
 
 #include <stddef.h>

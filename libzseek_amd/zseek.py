@@ -121,6 +121,7 @@ EXPORTED = [
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
     "zsk_zstd_compress_scratch_size", "zsk_zstd_compress_frames", "zsk_zstd_image_bound", "zsk_zstd_build_image",
+    "zsk_zstd_compress_scratch_size_ex", "zsk_zstd_compress_frames_ex",
 ]
 
 _lib = None
@@ -236,6 +237,11 @@ def lib() -> C.CDLL:
     L.zsk_zstd_compress_frames.restype = C.c_int
     L.zsk_zstd_compress_frames.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]
+    L.zsk_zstd_compress_scratch_size_ex.restype = C.c_size_t
+    L.zsk_zstd_compress_scratch_size_ex.argtypes = [C.c_uint32, C.c_uint64, C.c_int]
+    L.zsk_zstd_compress_frames_ex.restype = C.c_int
+    L.zsk_zstd_compress_frames_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]
     L.zsk_zstd_image_bound.restype = C.c_size_t
     L.zsk_zstd_image_bound.argtypes = [C.c_size_t, C.c_size_t, C.c_uint]
     L.zsk_zstd_build_image.restype = C.c_ssize_t
@@ -918,36 +924,47 @@ def zstd_compress_layout(sizes, src_offsets=None, flags=None) -> tuple[np.ndarra
     return d, int(slots.sum())
 
 
-def zstd_compress_scratch_size(nframes: int, src_bytes: int = 0) -> int:
-    return int(lib().zsk_zstd_compress_scratch_size(nframes, src_bytes))
+ZSTD_FORMAT_SUBSET = 0   # ZSK_ZSTD_FORMAT_SUBSET
+ZSTD_FORMAT_FULL = 1     # ZSK_ZSTD_FORMAT_FULL
 
 
-def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None = None) -> None:
+def zstd_compress_scratch_size(nframes: int, src_bytes: int = 0, full: bool = False) -> int:
+    if not full:
+        return int(lib().zsk_zstd_compress_scratch_size(nframes, src_bytes))
+    return int(lib().zsk_zstd_compress_scratch_size_ex(nframes, src_bytes, ZSTD_FORMAT_FULL))
+
+
+def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None = None, full: bool = False) -> None:
     """zsk_zstd_compress_frames on torch device tensors (async on the current
     stream): desc = COMPRESS_DESC_DTYPE bytes (uint8), src / dst uint8,
-    csize one int32 per frame (frame sizes out; 0 = refused descriptor)."""
+    csize one int32 per frame (frame sizes out; 0 = refused descriptor).
+    full=True: zsk_zstd_compress_frames_ex with ZSK_ZSTD_FORMAT_FULL."""
     import torch
     n = csize.numel()
     if desc.numel() != n * 24:
         raise ValueError("desc must hold 24 bytes per frame")
     if scratch is None:
-        scratch = torch.empty(max(zstd_compress_scratch_size(n, src.numel()), 1), dtype=torch.uint8,
+        scratch = torch.empty(max(zstd_compress_scratch_size(n, src.numel(), full), 1), dtype=torch.uint8,
                               device=csize.device)
     for t in (desc, src, dst, csize, scratch):
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError("zstd_compress_frames needs contiguous device tensors")
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
-    if lib().zsk_zstd_compress_frames(desc.data_ptr(), n, src.data_ptr(), dst.data_ptr(), csize.data_ptr(),
-                                      scratch.data_ptr(), scratch.numel(), stream) != 0:
+    args = (desc.data_ptr(), n, src.data_ptr(), dst.data_ptr(), csize.data_ptr(), scratch.data_ptr(),
+            scratch.numel(), stream)
+    r = lib().zsk_zstd_compress_frames_ex(*args, ZSTD_FORMAT_FULL) if full else lib().zsk_zstd_compress_frames(*args)
+    if r != 0:
         raise ZseekError("zsk_zstd_compress_frames launch failed")
 
 
 IMAGE_CONTENT_CHECKSUMS = 2   # ZSK_IMAGE_CONTENT_CHECKSUMS
+IMAGE_ZSTD_FULL = 4           # ZSK_IMAGE_ZSTD_FULL
 
 
-def _image_flags(checksums: bool, content_checksums: bool) -> int:
-    return (IMAGE_CHECKSUMS if checksums else 0) | (IMAGE_CONTENT_CHECKSUMS if content_checksums else 0)
+def _image_flags(checksums: bool, content_checksums: bool, full: bool = False) -> int:
+    return (IMAGE_CHECKSUMS if checksums else 0) | (IMAGE_CONTENT_CHECKSUMS if content_checksums else 0) | \
+        (IMAGE_ZSTD_FULL if full else 0)
 
 
 def zstd_image_bound(length: int, frame_size: int, checksums: bool = False) -> int:
@@ -956,9 +973,10 @@ def zstd_image_bound(length: int, frame_size: int, checksums: bool = False) -> i
 
 
 def zstd_build_image(src, frame_size: int, checksums: bool = False, content_checksums: bool = False,
-                     batch_bytes: int = 0, image=None):
+                     batch_bytes: int = 0, image=None, full: bool = False):
     """zsk_zstd_build_image: the uint8 device tensor `src` as a complete
     seekable zstd file in device memory (synchronous), as lz4_build_image.
+    full=True: the frames in ZSK_ZSTD_FORMAT_FULL (ZSK_IMAGE_ZSTD_FULL).
     -> the file, a view of `image`."""
     import torch
     if not src.is_cuda or not src.is_contiguous() or src.dtype != torch.uint8:
@@ -971,7 +989,7 @@ def zstd_build_image(src, frame_size: int, checksums: bool = False, content_chec
     torch.cuda.current_stream(src.device).synchronize()   # the bytes must be complete
     err = C.create_string_buffer(ERRBUF)
     n = lib().zsk_zstd_build_image(src.data_ptr() if src.numel() else None, src.numel(), frame_size,
-                                   _image_flags(checksums, content_checksums), batch_bytes, image.data_ptr(),
+                                   _image_flags(checksums, content_checksums, full), batch_bytes, image.data_ptr(),
                                    image.numel(), err)
     if n < 0:
         raise ZseekError(err.value.decode())
