@@ -24,37 +24,17 @@
 #include <stdint.h>
 
 #include "../../include/zseek_hip.h"
+#include "xxh64_dev.h"
 #include "zsk_internal.h"
 
 namespace zsk {
 
 namespace {
 
-constexpr uint64_t P1 = 0x9E3779B185EBCA87ull;
-constexpr uint64_t P2 = 0xC2B2AE3D27D4EB4Full;
-constexpr uint64_t P3 = 0x165667B19E3779F9ull;
-constexpr uint64_t P4 = 0x85EBCA77C2B2AE63ull;
-constexpr uint64_t P5 = 0x27D4EB2F165667C5ull;
+using namespace xxh64d;
 
 typedef uint64_t u64_ua __attribute__((aligned(1)));
 typedef uint32_t u32_ua __attribute__((aligned(1)));
-
-__device__ __forceinline__ uint64_t rotl(uint64_t x, int r)
-{
-    return (x << r) | (x >> (64 - r));
-}
-
-__device__ __forceinline__ uint64_t xround(uint64_t acc, uint64_t v)
-{
-    acc += v * P2;
-    return rotl(acc, 31) * P1;
-}
-
-__device__ __forceinline__ uint64_t xmerge(uint64_t h, uint64_t v)
-{
-    h ^= xround(0, v);
-    return h * P1 + P4;
-}
 
 __device__ __forceinline__ uint64_t ld8(const uint8_t *p)
 {
@@ -70,7 +50,7 @@ template <typename Sink>
 __device__ __forceinline__ void frame_xxh64(const uint8_t *p, uint32_t len, bool on, uint32_t k, Sink sink)
 {
     const uint32_t stripes = len / 32;
-    uint64_t acc = k == 0 ? P1 + P2 : k == 1 ? P2 : k == 2 ? 0 : 0ull - P1;
+    uint64_t acc = k == 0 ? P64_1 + P64_2 : k == 1 ? P64_2 : k == 2 ? 0 : 0ull - P64_1;
     const uint8_t *q = p + 8 * k;
     uint32_t s = 0;
     for (; s + 4 <= stripes; s += 4) {
@@ -91,35 +71,30 @@ __device__ __forceinline__ void frame_xxh64(const uint8_t *p, uint32_t len, bool
         return;
     uint64_t h;
     if (len >= 32) {
-        h = rotl(acc, 1) + rotl(a1, 7) + rotl(a2, 12) + rotl(a3, 18);
+        h = rotl64(acc, 1) + rotl64(a1, 7) + rotl64(a2, 12) + rotl64(a3, 18);
         h = xmerge(h, acc);
         h = xmerge(h, a1);
         h = xmerge(h, a2);
         h = xmerge(h, a3);
     } else {
-        h = P5;
+        h = P64_5;
     }
     h += len;
     uint32_t i = stripes * 32;
     for (; i + 8 <= len; i += 8) {
         h ^= xround(0, ld8(p + i));
-        h = rotl(h, 27) * P1 + P4;
+        h = rotl64(h, 27) * P64_1 + P64_4;
     }
     if (i + 4 <= len) {
-        h ^= (uint64_t)*reinterpret_cast<const u32_ua *>(p + i) * P1;
-        h = rotl(h, 23) * P2 + P3;
+        h ^= (uint64_t)*reinterpret_cast<const u32_ua *>(p + i) * P64_1;
+        h = rotl64(h, 23) * P64_2 + P64_3;
         i += 4;
     }
     for (; i < len; i++) {
-        h ^= p[i] * P5;
-        h = rotl(h, 11) * P1;
+        h ^= p[i] * P64_5;
+        h = rotl64(h, 11) * P64_1;
     }
-    h ^= h >> 33;
-    h *= P2;
-    h ^= h >> 29;
-    h *= P3;
-    h ^= h >> 32;
-    sink((uint32_t)h);
+    sink((uint32_t)xavalanche(h));
 }
 
 __global__ __launch_bounds__(256) void frame_xxh64_kernel(const FrameDesc *__restrict__ desc, uint32_t n,

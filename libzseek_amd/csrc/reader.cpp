@@ -13,7 +13,7 @@
 //                                           compressed span, pinned staging)
 //   LZ4F_decompress / ZSTD_decompress*      HIP kernels over the batch (LZ4:
 //   on the CPU                              lz4_*.hip + seq_exec.hip; zstd:
-//                                           zstd_decode.hip + seq_exec.hip)
+//                                           zstd_*.hip + seq_exec.hip)
 //   serial                                  a pipeline of kSlots batches per
 //                                           device: the user pread of batch
 //                                           k+1, the upload / decode / download

@@ -15,7 +15,7 @@
 // A seekable file in device memory (zsk_reader_open_device): the frames are
 // decoded where they are.  The decode kernels get `base`, the image's start
 // rounded down to 256 bytes (the alignment of the hipMalloc'd staging they
-// otherwise read: zstd_decode.hip aligns its spans by c_off alone, so the base
+// otherwise read: the zstd kernels align their spans by c_off alone, so the base
 // itself must be 16-byte aligned), and descriptors whose c_off carry `bias`.
 struct DeviceImage {
     const uint8_t *ptr = nullptr;    // the caller's image (not owned)

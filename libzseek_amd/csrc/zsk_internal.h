@@ -272,8 +272,9 @@ int launch_seq_exec_lit(const FrameDesc *d_desc, uint32_t nframes, const uint8_t
                         const uint32_t *nitems, int32_t *d_status, hipStream_t stream, bool one = false,
                         uint32_t max_dsize = 0xFFFFFFFFu, uint32_t stop_last = 0xFFFFFFFFu);
 
-// zstd decoder (zstd_decode.hip): plan (item bounds -> rec_base[0..n]) and
-// decode (frame kernel -> items + literal scratch, execute, checksums).
+// zstd decoder (zstd_plan.hip, zstd_decode.hip): plan (item bounds ->
+// rec_base[0..n]) and decode (frame kernel -> items + literal scratch,
+// execute, checksums).  The stage launchers are in zstd_internal.h.
 struct ZstdScratch {
     uint32_t *bound = nullptr;     // per-frame item bound
     uint32_t *bblk = nullptr;      // per-frame block count (plan)
@@ -293,9 +294,6 @@ struct ZstdScratch {
     // those, zstd_one_kernel's finished-workgroup counter (zero between launches)
     uint64_t *d_total = nullptr;
     uint64_t *total = nullptr;     // pinned host copy of d_total
-    uint64_t *h_plan = nullptr;    // pinned: a host plan's rec_base then blk_base (zstd_decode_frames_host)
-    uint64_t h_plan_cap = 0;       //   (u64 entries)
-    uint64_t *d_plan = nullptr;    // its device copy (one upload), 2 (kOneMaxFrames + 1) entries
     hipStream_t side = nullptr;    // the Huffman kernel's stream (beside the sequence replay)
     hipStream_t sq = nullptr;      // the sequence kernel's stream
     static constexpr int kChunks = 8;   // most chunks a decode runs in
@@ -355,16 +353,12 @@ int zstd_decode_frames(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
                        uint32_t *d_fail_at = nullptr, uint32_t stop_last = 0xFFFFFFFFu);
 // The same for a request's few frames whose compressed bytes are also in host
 // memory (h_desc / h_comp: the reader's pinned upload, the same layout as
-// d_desc / d_comp): the plan -- zstd_plan_kernel's per-frame bounds, the scans,
-// the totals -- computed on the host, so the decode needs no plan launch and
-// no synchronization.  nframes <= kOneMaxFrames.
-int zstd_decode_frames_host(const FrameDesc *h_desc, const uint8_t *h_comp, const FrameDesc *d_desc,
-                            uint32_t nframes, const uint8_t *d_comp, uint8_t *d_out, int32_t *d_status,
-                            ZstdScratch *s, hipStream_t stream, uint32_t *d_fail_at,
-                            uint32_t stop_last = 0xFFFFFFFFu);
-// ... in two steps, for a caller that uploads the plan with its own bytes:
-// the plan (2 (nframes + 1) u64: item slot offsets, then block slot offsets)
-// into h_plan before the upload, then the decode with the plan's device copy
+// d_desc / d_comp): the plan -- zstd_plan_kernel's per-frame bounds
+// (zstd_plan.h), the scans, the totals -- computed on the host, so the decode
+// needs no plan launch and no synchronization.  nframes <= kOneMaxFrames.  In
+// two steps, for a caller that uploads the plan with its own bytes: the plan
+// (2 (nframes + 1) u64: item slot offsets, then block slot offsets) into
+// h_plan before the upload, then the decode with the plan's device copy
 struct ZstdHostPlan {
     uint64_t items, blocks, extent, dmax;
     bool cks;   // some frame carries a content checksum

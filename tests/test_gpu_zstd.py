@@ -323,7 +323,7 @@ def test_zstd_readers_concurrent(gpu, zs):
     """Readers opened, read and closed from several threads at once, and one
     reader shared by them (the reader serialises its own preads): every read
     bit-exact.  Exercises the pooled Huffman side stream (zstd_decode.hip
-    side_acquire / side_release) under interleaved open/close."""
+    side_create / side_destroy) under interleaved open/close."""
     import threading
     data = zs.synth_buffer(48 * 65536 + 1234)
     img = bytes(zs.zstd_seekable(data, 65536).tobytes())

@@ -362,7 +362,7 @@ def test_preadv_device(gpu, zs, record):
 @pytest.mark.parametrize("path", ["host", "device"])
 def test_long_images(gpu, zs, record, maker, path):
     """each small case with 33 intact entries on each side (67 entries: past
-    the one-frame route, so the reader's host plan, zstd_plan_frame_host, sees
+    the one-frame route, so the reader's host plan, zstd_host_plan, sees
     the crafted entry among others; the device plan, zstd_plan_kernel, sees it
     in every zsk_zstd_decode_frames batch above), one range per entry in one
     vectored read, from a host image and from one in device memory"""

@@ -469,6 +469,8 @@ def frame_header(fcs=None, fcs_bytes=None, single=None, window=None, dict_id=Non
         single = fcs_bytes is not None
     did = {0: 0, 1: 1, 2: 2, 4: 3}[dict_bytes]
     fhd = flag << 6 | (1 if single else 0) << 5 | unused << 4 | reserved << 3 | (1 if checksum else 0) << 2 | did
+    # (the table's checksummed frames all come from Frame.build, which records them)
+    assert not (checksum and _recording and not _in_build)
     out = MAGIC + bytes([fhd])
     if not single:
         out += bytes([0x50 if window is None else window])
@@ -490,7 +492,10 @@ def block(typ: int, payload: bytes, last: bool, size=None) -> bytes:
 
 
 def skippable(data: bytes = b"", nibble=0, size=None) -> bytes:
-    return (0x184D2A50 | nibble).to_bytes(4, "little") + (len(data) if size is None else size).to_bytes(4, "little") + data
+    out = (0x184D2A50 | nibble).to_bytes(4, "little") + (len(data) if size is None else size).to_bytes(4, "little") + data
+    if _recording and size is None:
+        BUILT[out] = None
+    return out
 
 
 def checksum_of(content: bytes) -> bytes:
@@ -521,6 +526,31 @@ class Cb:
                  nform=None, payload=None):
         self.lits, self.seqs, self.lit, self.lform, self.huf, self.hdesc = bytes(lits), list(seqs), lit, lform, huf, hdesc
         self.modes, self.nform, self.payload = modes, nform, payload
+
+
+# The builder's record of what it wrote while the table below was made: every
+# whole frame -> (its blocks as model() gives them, its checksum flag), every
+# whole skippable frame -> None.  _add takes each accepted entry apart into
+# these, so RECORDS has the frames, block by block, of all of them.
+BUILT: dict = {}
+_recording = _in_build = False
+# accepted case -> (per frame its blocks, as expand() and items() take them;
+# some frame carries the checksum flag)
+RECORDS: dict = {}
+
+
+def _record_of(name, entry):
+    """the frames and skippable frames the entry was put together from"""
+    frames, cks, p = [], False, 0
+    while p < len(entry):
+        hit = max((k for k in BUILT if entry.startswith(k, p)), key=len, default=None)
+        if hit is None:
+            return None
+        if BUILT[hit] is not None:
+            frames.append(BUILT[hit][0])
+            cks = cks or BUILT[hit][1]
+        p += len(hit)
+    return frames, cks
 
 
 class Frame:
@@ -605,7 +635,10 @@ class Frame:
                 hdr["fcs_bytes"] = 1 if n < 256 else 2 if n < 65792 else 4
                 if hdr["fcs_bytes"] == 1 and hdr.get("single") is False:
                     hdr["fcs_bytes"] = 4        # (the 1-byte form is the single-segment one)
+        global _in_build
+        _in_build = True
         out = frame_header(**hdr)
+        _in_build = False
         for i, b in enumerate(blocks):
             fin = last and i + 1 == len(blocks)
             if isinstance(b, Raw):
@@ -616,6 +649,8 @@ class Frame:
                 out += block(2, self.cblock(b), fin)
         if hdr.get("checksum"):
             out += checksum_of(content)
+        if _recording and last:
+            BUILT[bytes(out)] = (model(blocks), bool(hdr.get("checksum")))
         return out
 
 
@@ -675,7 +710,7 @@ def expand(frames, clamp: bool = True) -> bytes:
 
 
 def items(frames, pad_slot: int = 63):
-    """The item slots the replay gives an entry (lemit in zstd_decode.hip, and
+    """The item slots the replay gives an entry (lemit in zstd_seq_dev.h, and
     the wave form's scan): per emit (slot, extended, padded).  One item per
     sequence, per block's literal tail and per raw / RLE block that is not
     empty; two where it is extended (literals > 255, match > 258, a match of
@@ -808,6 +843,9 @@ def _add(name, entry, want=None, code=0, dsize=None):
         if not isinstance(want, (bytes, bytearray)):
             MODELS[name] = want
         CASES.append((name, bytes(entry), len(exp) if dsize is None else dsize, bytes(exp), 0))
+        # (a frame put together by hand: the model given for it, block by block; no checksum flag)
+        RECORDS[name] = _record_of(name, bytes(entry)) or (want, False)
+        assert isinstance(RECORDS[name][0], list), name
     else:
         assert dsize is not None, name
         CASES.append((name, bytes(entry), dsize, None, code))
@@ -836,6 +874,9 @@ HEAD = (8, O(8), 5)     # 8 literals, then a match that copies the first 5
 
 def _make_cases():
     L = lits
+    # the seed frames below, written out by hand: a raw block; a compressed one with one sequence
+    BUILT[A] = ([b"abcdefgh"], False)
+    BUILT[B1] = ([(b"x", [(1, O(1), 3)])], False)
     # --- h. entry and frame header ----------------------------------------
     for n, fb in ((0, 1), (255, 1), (256, 2), (65791, 2), (65792, 4)):
         _add(f"h_fcs{n}_in{fb}", frame([Raw(L(n, 1))], fcs=n, fcs_bytes=fb), L(n, 1))
@@ -929,7 +970,8 @@ def _make_cases():
           _add("b_comp131072", frame_header() + block(2, lit_raw(big + b"!") + b"\0", True), None, 72, 131068))
     _add("b_type3", frame_header() + block(3, b"abc", True), None, 20, 3)
     _add("b_1000_empty_raw", frame([Raw(b"")] * 1000 + [Raw(L(50, 8))]), L(50, 8))
-    _add("b_1000_empty_then_seqs", frame([Raw(b"")] * 1000 + [Cb(L(9, 8), [HEAD])]), [[(L(9, 8), [HEAD])]])
+    _add("b_1000_empty_then_seqs", frame([Raw(b"")] * 1000 + [Cb(L(9, 8), [HEAD])]),
+         [[b""] * 1000 + [(L(9, 8), [HEAD])]])
     _add("b_last_then_more", frame([Raw(L(10))]) + block(0, L(5), True), None, 72, 15)
     _add("b_no_last_block", frame([Raw(L(10)), Raw(L(5))], last=False), None, 72, 15)
     _add("b_block_cut", frame([Raw(L(10))])[:-1], None, 72, 10)
@@ -1215,7 +1257,8 @@ def _make_cases():
     # count 0 in the 2-byte form: libzstd goes on to read a mode byte
     _add("s_count0_in2", frame_header() + block(2, lit_raw(l5) + nseq_bytes(0, 2), True), None, 72, 28)
     # ... and with one (and whatever follows it) takes the block as literals only
-    _pair(_add("s_count0_in2_mode_byte", frame_header() + block(2, lit_raw(l5) + nseq_bytes(0, 2) + b"\0junk", True), l5),
+    _pair(_add("s_count0_in2_mode_byte", frame_header() + block(2, lit_raw(l5) + nseq_bytes(0, 2) + b"\0junk", True),
+                   [[(l5, [])]]),
           "s_count0_in2")
     _add("s_count0_in2_rep_mode", frame_header() + block(2, lit_raw(l5) + nseq_bytes(0, 2) + b"\xfc", True), None, 20, 28)
     pay = lit_raw(l5) + nseq_bytes(0)
@@ -1326,7 +1369,9 @@ def _make_cases():
     NEIGHBOURS.append((frame(nb, single=False, checksum=True), expand([model(nb)])))
 
 
+_recording = True
 _make_cases()
+_recording = False
 CASE = {c[0]: c for c in CASES}
 
 
