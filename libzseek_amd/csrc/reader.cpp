@@ -1018,9 +1018,16 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
             e = hipErrorLaunchFailure;
     } else if (a.h_desc && split_scratch_reserve(&s.split, a.n, split_items_needed(a.h_desc, a.n), a.q) != 0) {
         e = hipErrorOutOfMemory;
-    } else if (launch_lz4_split(a.d_desc, a.n, a.comp, s.d_out, s.d_status, d_fail, a.q, &s.split, ROUTE_AUTO, 15, 0,
-                                a.stop_last, a.max_dsize, a.post, a.posted, a.in_order, !a.in_order) != 0) {
-        e = hipErrorLaunchFailure;
+    } else {
+        Lz4Request rq;
+        rq.nframes = a.n;
+        rq.stop_last = a.stop_last;
+        rq.max_dsize = a.max_dsize;
+        rq.in_order = a.in_order;
+        rq.scan_layout = !a.in_order;
+        rq.post = a.post != nullptr;
+        if (launch_lz4_split(rq, {a.d_desc, a.comp, s.d_out, s.d_status, d_fail}, a.q, &s.split, a.post, a.posted) != 0)
+            e = hipErrorLaunchFailure;
     }
     // seek-table checksums (descriptor bit 7) when asked for: XXH64 low 32
     // bits of every decoded frame, on the GPU (frame_check.hip)

@@ -21,15 +21,14 @@ int staged(int stages, int route, int tune, const FrameDesc *d_desc, uint32_t nf
            const uint8_t *d_comp, uint8_t *d_out, int32_t *d_status, hipStream_t stream)
 {
     std::lock_guard<std::mutex> g(g_mu);
-    uint64_t want = (uint64_t)nframes * slots_of(65536 + 64);
-    if (want > (512ull << 20))
-        want = 512ull << 20;
-    if (g_s.total && *g_s.total > want)
-        want = *g_s.total;
-    if (split_scratch_reserve(&g_s, nframes, want, stream) != 0)
+    if (split_scratch_reserve(&g_s, nframes, split_items_default(&g_s, nframes), stream) != 0)
         return -1;
-    return launch_lz4_split(d_desc, nframes, d_comp, d_out, d_status, nullptr, stream, &g_s, route,
-                            stages, tune);
+    Lz4Request rq;
+    rq.nframes = nframes;
+    rq.route = route;
+    rq.stages = stages;
+    rq.tune = tune;
+    return launch_lz4_split(rq, {d_desc, d_comp, d_out, d_status, nullptr}, stream, &g_s);
 }
 // Parse / execute overlap (verdict r04 item 4): the plan on the caller's
 // stream, then K frame chunks: chunk c's lean parse on a second stream, its
@@ -50,14 +49,12 @@ int overlapped(uint32_t K, const FrameDesc *d_desc, uint32_t nframes, const uint
     }
     if (K < 1 || K > 16)
         return -1;
-    uint64_t want = (uint64_t)nframes * slots_of(65536 + 64);
-    if (want > (512ull << 20))
-        want = 512ull << 20;
-    if (g_s.total && *g_s.total > want)
-        want = *g_s.total;
-    if (split_scratch_reserve(&g_s, nframes, want, stream) != 0)
+    if (split_scratch_reserve(&g_s, nframes, split_items_default(&g_s, nframes), stream) != 0)
         return -1;
-    if (launch_lz4_split(d_desc, nframes, d_comp, d_out, d_status, nullptr, stream, &g_s, ROUTE_AUTO, 1, 0) != 0)
+    Lz4Request plan_only;
+    plan_only.nframes = nframes;
+    plan_only.stages = 1;
+    if (launch_lz4_split(plan_only, {d_desc, d_comp, d_out, d_status, nullptr}, stream, &g_s) != 0)
         return -1;
     if (hipEventRecord(ev[16], stream) != hipSuccess || hipStreamWaitEvent(ps, ev[16], 0) != hipSuccess)
         return -1;

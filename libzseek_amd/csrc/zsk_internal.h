@@ -9,6 +9,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/zseek_hip.h"
+#include "lz4_route.h"
 
 namespace zsk {
 
@@ -63,18 +64,6 @@ inline uint32_t status_max_block(int32_t st)
 // profiler output.
 const char *lz4_kernel_name(uint32_t nframes);
 
-// Production decoders a batch can be forced through (tests; ROUTE_AUTO is the
-// library's own choice).  LEAN / SCAN / CHUNK: the two-phase decoder with that
-// parse for every frame.
-// BLOCK: every multi-block-capable frame through the block route below (any
-// batch size, no job minimum).
-// ONE: the one-frame route (batches of <= kOneMaxFrames frames under AUTO):
-// every frame takes the chunk parse, reading the frame staged whole in LDS
-// (one frame per workgroup); no plan scan, no lean / scan launches.
-enum : int { ROUTE_AUTO = 0, ROUTE_WAVE = 1, ROUTE_LEAN = 2, ROUTE_SCAN = 3, ROUTE_CHUNK = 4, ROUTE_BLOCK = 5,
-             ROUTE_ONE = 6 };
-constexpr uint32_t kOneMaxFrames = 64;
-
 // Launch the LZ4 frame decoder over nframes frames (asynchronous on stream).
 // d_fail_at (optional) receives, per frame, the output offset of the block
 // whose decode failed.  tune: tuning builds only (0 = production kernels).
@@ -109,7 +98,6 @@ struct BlockRes {
 };
 static_assert(sizeof(BlockJob) == 32 && sizeof(BlockRes) == 16, "block job layout");
 constexpr uint32_t kNoJob = 0xFFFFFFFFu;
-constexpr uint32_t kMaxBlockJobs = 64;   // blocks per frame the route takes
 
 struct SplitScratch {
     uint64_t *rec_base = nullptr;   // [frames_cap]
@@ -138,25 +126,22 @@ uint64_t split_items_needed(const FrameDesc *h_desc, uint32_t n);
 // Grow scratch to at least (frames, items); stream-ordered.  0 on success.
 int split_scratch_reserve(SplitScratch *s, uint32_t frames, uint64_t items, hipStream_t stream);
 void split_scratch_free(SplitScratch *s);
+// Item slots to reserve when the frames' sizes are unknown: `known` when the
+// caller has a bound (0: none -- then 64 KiB frames, at most 512 Mi slots),
+// and never below the item total the previous plan on s reported.
+uint64_t split_items_default(const SplitScratch *s, uint32_t nframes, uint64_t known = 0);
 
-// Parse routing of the two-phase decoder: frames of >= chunk_min compressed
-// bytes take lz4_chunk_kernel, of [lean_min, chunk_min) lz4_lean_kernel,
-// shorter ones lz4_scan_kernel.
-struct ParseRoute {
-    uint32_t chunk_min, lean_min;
-};
-ParseRoute parse_route(uint32_t nframes, int route);
-// The parse kernel a frame of c_size compressed bytes takes in a batch of
-// nframes (what a kernel trace shows), for tooling.
+// The routing decision (lz4_route.h: lz4_plan) over this process's
+// environment switches, read once.  parse_kernel_name: the parse kernel a
+// frame of c_size compressed bytes takes in a batch of nframes (what a kernel
+// trace shows), for tooling; lz4_pick_engine: never ENGINE_AUTO.
+const Lz4Switches &lz4_switches();
 const char *parse_kernel_name(uint32_t nframes, uint32_t c_size, int route = ROUTE_AUTO);
+int lz4_pick_engine(uint32_t nframes);
 
-// stop_last: the batch's last frame is executed only until it has produced
-// that many bytes (its status still covers the whole frame; the reader's
-// no-cache requests ending inside it).
-// Two-phase decoder with caller-owned scratch (must cover nframes and the
-// frames' item slots; frames that do not fit are decoded by the wave kernel).
-// stages: bitmask 1 plan, 2 parse, 4 execute, 8 hand-offs (tuning builds
-// time subsets).
+// Two-phase decoder with caller-owned scratch (must cover rq.nframes and the
+// frames' item slots; frames that do not fit are decoded by the wave kernel):
+// the launches lz4_plan(rq, lz4_switches()) lists, on `stream`.
 // A lone frame's results straight into the reader's pinned buffers from the
 // one-frame route's execute (no download kernel, no launch behind it): its
 // status and fail_at to h_status[0..1], decoded bytes [h_from, h_from +
@@ -169,22 +154,26 @@ struct HostPost {
     uint32_t *h_flag = nullptr;
     uint32_t seq = 0;
 };
-int launch_lz4_split(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
-                     uint8_t *d_out, int32_t *d_status, uint32_t *d_fail_at,
-                     hipStream_t stream, SplitScratch *s, int route = ROUTE_AUTO, int stages = 15,
-                     int tune = 0, uint32_t stop_last = 0xFFFFFFFFu, uint32_t max_dsize = 0xFFFFFFFFu,
-                     const HostPost *post = nullptr, bool *posted = nullptr, bool in_order = false,
-                     bool scan_layout = false);
-// (in_order: the caller laid the frames out in order in d_comp -- the
-// one-frame route's chunk parse then does the plan's work, no plan launch.
-// max_dsize: the batch's largest decoded frame when the caller knows it --
+struct Lz4Buffers {
+    const FrameDesc *d_desc;
+    const uint8_t *d_comp;
+    uint8_t *d_out;
+    int32_t *d_status;
+    uint32_t *d_fail_at;   // optional
+};
+int launch_lz4_split(const Lz4Request &rq, const Lz4Buffers &b, hipStream_t stream, SplitScratch *s,
+                     const HostPost *post = nullptr, bool *posted = nullptr);
+// (rq, lz4_route.h.  stop_last: the batch's last frame is executed only until
+// it has produced that many bytes -- its status still covers the whole frame;
+// the reader's no-cache requests ending inside it.  in_order: the one-frame
+// route's chunk parse then does the plan's work, no plan launch.  max_dsize:
 // the one-frame route then skips the wave execute for frames of <= 64 KiB.
-// post: a one-frame batch's results to the host from its execute, when the
-// batch takes that route (*posted = true; else the caller downloads).
-// scan_layout: the plan lays the item slots out by its scan of
-// slots_of(c_size) whatever the frames' order -- frames scattered over a
-// device image then take sum(slots_of(c_size)) slots, not the compressed
-// distance they span / 8; not with in_order)
+// post (rq.post says it was offered): a one-frame batch's results to the host
+// from its execute, when the batch takes that route (*posted = true; else the
+// caller downloads).  scan_layout: the plan lays the item slots out by its
+// scan of slots_of(c_size) whatever the frames' order -- frames scattered
+// over a device image then take sum(slots_of(c_size)) slots, not the
+// compressed distance they span / 8)
 
 // Item slots of a frame in the split decoder's scratch.  An item is 8 bytes;
 // a sequence takes one (two when extended), a stored block two.  LZ4 data
@@ -196,10 +185,7 @@ __host__ __device__ __forceinline__ uint32_t slots_of(uint32_t c_size)
     return (c_size / 8 + 32 + 3) & ~3u;
 }
 
-// Decoder selection (env ZSEEK_HIP_KERNEL = split | wave; default auto).
-enum : int { ENGINE_AUTO = 0, ENGINE_SPLIT, ENGINE_WAVE };
-
-// Per-stage launch timing: stages [plan, parse, execute, hand-off]; marks
+// Per-stage launch timing (stage_timer.cpp): stages [plan, parse, execute, hand-off]; marks
 // 0..4 are the boundaries, recorded as HIP events on the launch's stream
 // while enabled.  Slots kTimedStages.. are per-kernel spans a launch sums
 // over its chunks (zstd: frame, sequence, Huffman and execute kernels, each
@@ -222,8 +208,6 @@ hipError_t hip_event_get(hipEvent_t *e);
 void hip_event_put(hipEvent_t e);
 int kernel_timing(int on);
 int kernel_times(double *ms, int cap);
-int lz4_engine();
-int lz4_pick_engine(uint32_t nframes);   // never ENGINE_AUTO
 
 // Execute phase (seq_exec.hip): one wave per frame, linear per-wave LDS
 // stage, DPP scans, piece descriptors.  version: tuning builds only (0 = the
@@ -384,10 +368,6 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
                     const uint64_t *rec_base, uint64_t capacity, uint64_t *items, uint32_t *nitems,
                     int32_t *d_status, uint32_t *d_fail_at, hipStream_t stream, uint32_t max_csize,
                     int diag = 0, uint32_t min_csize = 0);
-// Frames under this many compressed bytes take the older lz4_scan_kernel
-// (its direct item stores beat the lean kernel's line flush on short frames:
-// 4 KiB frames 5.68 vs 6.71 ms per launch, config 3)
-constexpr uint32_t kLeanMinCsize = 12288;
 // Block route parse: lane per job of s->jobs (the first *s->njobs), all
 // lanes idle when fewer than min_jobs jobs were planned.
 int launch_lz4_lean_blocks(const FrameDesc *d_desc, const uint8_t *d_comp, const uint64_t *rec_base,
@@ -418,13 +398,6 @@ int launch_lz4_chunk(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d
 // (one && solo_total: the batch has no plan launch -- one frame, or frames
 // the caller laid out in order; each workgroup lays its frame's slots out by
 // the plan's in-order formula and the last reports their total there)
-// Frames of at least chunk_parse_min(nframes) compressed bytes go to the
-// chunk parse: with >= 32768 frames the lane-per-frame scan has a lane for
-// every frame it needs and wins on 64 KiB frames (2.07 vs 4.18 ms parse at
-// config 2); smaller batches and bigger frames leave its lanes idle
-// (1 MiB frames: 4,096 chains; 256 MiB batches: 4,096 frames).
-// Env ZSEEK_PARSE=scan|chunk forces one parse for every frame.
-uint32_t chunk_parse_min(uint32_t nframes);
 
 // Wave-per-frame kernel over only the frames whose status is ST_NOT_RUN
 // (the split decoder's hand-offs).

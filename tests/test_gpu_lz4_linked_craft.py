@@ -147,7 +147,7 @@ def test_origin_scratch_limit(gpu, zs, table):
     origin scratch (kOriginJobsMax jobs), in one batch of the one-frame route:
     the frames whose jobs lie inside the scratch go block-parallel, the rest
     through the windowed execute (seq_exec_big_kernel); all bytes right."""
-    with open(os.path.join(ROOT, "libzseek_amd", "csrc", "lz4_split.hip")) as f:
+    with open(os.path.join(ROOT, "libzseek_amd", "csrc", "lz4_route.h")) as f:
         limit = int(re.search(r"constexpr uint32_t kOriginJobsMax = (\d+);", f.read()).group(1))
     n = limit // 64 + 1
     assert (n - 1) * 64 <= limit < n * 64 and n == 17
