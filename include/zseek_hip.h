@@ -13,6 +13,10 @@
  *   zsk_zstd_decode_frames — ZSTD_decompressDCtx (decompress.c:537) /
  *                            ZSTD_decompressStream (:414-454), batched the
  *                            same way.
+ *   zsk_zstd_decode_frames_async — the same decode without its host wait:
+ *                            scratch sized from bounds the caller states
+ *                            (zsk_zstd_bounds_default: a policy), the plan
+ *                            checked against them on the device.
  *   zsk_reader_frames      — the seek-table accessors frame_offset_c/d and
  *                            frame_size_c/d, seek_table.c:204-226.
  *   zsk_pread_device       — zseek_pread (decompress.c:806-824) with the
@@ -23,7 +27,8 @@
  *                            in one grid per batch; zsk_gather_segments is
  *                            its device-side segmented copy.
  *   zsk_preadv_device_async — the same read queued on the caller's stream,
- *                            its per-range results left in device memory.
+ *                            its per-range results left in device memory
+ *                            (a zstd reader: after zsk_reader_set_zstd_async).
  *   zsk_preadv_device_indirect — ... with the range list in device memory
  *                            too, planned by kernels from the seek table a
  *                            device-image reader keeps resident.
@@ -104,6 +109,53 @@ ZSEEK_EXPORT int zsk_zstd_decode_frames(const zsk_frame_desc_t *d_desc,
     uint32_t nframes, const void *d_comp, void *d_out, int32_t *d_status,
     void *stream);
 #define ZSK_STATUS_ZSTD 0x4000000 /* zstd frame failure: low bits = ZSTD_ErrorCode */
+
+/*
+ * zsk_zstd_decode_frames, stream-ordered.  The descriptors, per-frame statuses
+ * and decoded bytes are zsk_zstd_decode_frames'.  Everything is queued on
+ * @stream, ordered after what the stream already holds and before what is
+ * queued later; the call returns 0 once everything is queued and never waits
+ * for the planning kernel.  Instead the caller states @bounds, the host sizes
+ * the scratch and the Huffman grids from them before anything is queued, and
+ * the device checks its own plan against them behind the planning kernel.
+ *
+ * A batch that does not fit -- more block headers than max_blocks, more item
+ * slots than max_blocks and max_sequences provide, or a frame reaching past
+ * out_bytes -- is refused on the device: every d_status[f] of the call becomes
+ * ZSK_ERR_SCRATCH, no byte of @d_out is written, and the next call decodes as
+ * if nothing had happened.  The remedy is zsk_zstd_decode_frames, which sizes
+ * exactly.  (A refused call's statuses read ZSK_ERR_SCRATCH only once the
+ * stream has passed the call's last kernel.)
+ *
+ * zsk_zstd_bounds_default fills @b for @nframes entries decoding into
+ * @out_bytes: max_sequences = out_bytes / 3 (a zstd match is at least 3 bytes,
+ * so no entry that decodes within out_bytes has more), max_blocks = 2 *
+ * nframes + out_bytes / 16384 (libzstd and this project's compressor write
+ * 128 KiB blocks: 8x their rate plus two per entry).  A policy, not a
+ * guarantee: an entry of many tiny blocks exceeds it and is refused as above.
+ * Memory: items are 8 bytes each, two per sequence plus padding -- about 5.4
+ * bytes per output byte at the defaults -- a block costs about 11 KiB (table
+ * slot, Huffman jobs, ops), and the literal scratch is out_bytes + 64.  A
+ * caller who knows its files states tighter bounds.
+ *
+ * Host waits: only growing the pooled scratch, at first use or after a call
+ * with larger bounds (freeing device memory waits for the device) -- the wait
+ * zsk_preadv_device_async lists as its (1).  The scratch comes from the pool
+ * zsk_zstd_decode_frames uses (at most four sets per device, reused in stream
+ * order).  -1 and nothing queued for: NULL @bounds; a stream that is capturing
+ * (pooled scratch sized per call: it must never end up in a graph); bounds no
+ * device could hold (max_blocks >= 2^29); an allocation or launch failure.
+ * nframes == 0 returns 0 and queues nothing.
+ */
+#define ZSK_ERR_SCRATCH 105   /* the batch did not fit the call's bounds: nothing of the call was decoded */
+typedef struct {
+    uint64_t out_bytes;      /* every frame's [d_off, d_off + d_size) lies inside d_out[0, out_bytes) */
+    uint64_t max_blocks;     /* zstd block headers in all entries of the call together */
+    uint64_t max_sequences;  /* sequences (as declared in the sequence sections) in all of them together */
+} zsk_zstd_bounds_t;
+ZSEEK_EXPORT void zsk_zstd_bounds_default(uint32_t nframes, uint64_t out_bytes, zsk_zstd_bounds_t *b);
+ZSEEK_EXPORT int zsk_zstd_decode_frames_async(const zsk_frame_desc_t *d_desc, uint32_t nframes,
+    const void *d_comp, void *d_out, int32_t *d_status, const zsk_zstd_bounds_t *bounds, void *stream);
 
 /* Human-readable name of a frame status (LZ4F-style "ERROR_..." names for
  * LZ4 frames, ZSTD_getErrorName strings for zstd frames). */
@@ -259,15 +311,16 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf,
  * the GPU counters (batches, frames_decoded, bytes_decoded, bytes_uploaded)
  * advance at enqueue.
  *
- * LZ4 readers only, over a host image or a device image
- * (zsk_reader_open_device).  A zstd reader: -1, "asynchronous read: zstd is
- * not supported".  On a host image the pread callbacks run on the calling
+ * LZ4 readers, over a host image or a device image (zsk_reader_open_device).
+ * A zstd reader: -1, "asynchronous read: zstd is not supported", unless
+ * zsk_reader_set_zstd_async has turned it on (below).  On a host image the pread callbacks run on the calling
  * thread during the call, one per run of adjacent touched frames; only the
  * GPU work is deferred.
  *
  * -1 and nothing queued for: a NULL reader ("invalid reader"); a stream that
  * is capturing ("asynchronous read: stream is capturing" -- the call reuses
- * pinned staging, so it must never end up in a graph); a zstd reader; NULL
+ * pinned staging, so it must never end up in a graph); a zstd reader without
+ * zsk_reader_set_zstd_async; NULL
  * @ranges or NULL @d_result with nranges > 0; NULL @d_buf when some range has
  * bytes ("invalid buffer"); no device.  nranges == 0 returns 0 and queues only
  * d_result[0] = 0 (nothing for a NULL @d_result).  The call may also fail
@@ -295,6 +348,27 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device(zseek_reader_t *reader, void *d_buf,
 ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf,
     const zsk_range_t *ranges, size_t nranges, int64_t *d_result, void *stream,
     void *call_data, char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * zsk_preadv_device_async on a zstd reader.  Off by default (@seq_bytes 0:
+ * the refusal above).  @seq_bytes >= 3 turns it on; 1 and 2 return false, as
+ * does a NULL reader.  Env ZSEEK_ZSTD_ASYNC=<n> at open does the same.
+ *
+ * When on, each batch of the call is decoded by zsk_zstd_decode_frames_async's
+ * machinery on the batch slot's own scratch -- no host plan, no wait -- with
+ * bounds taken from the seek table: out_bytes the batch's decoded span,
+ * max_sequences = span / seq_bytes, max_blocks the sum over its frames of
+ * 2 + d_size / 16384.  With 3, no file that decodes overflows the sequence
+ * bound; larger values save memory (16 / seq_bytes bytes of items per decoded
+ * byte) and give that guarantee up.  A batch that does not fit its bounds
+ * is refused whole on the device: its frames carry ZSK_ERR_SCRATCH, its ranges
+ * come out short or -1 like any failed frame's, and d_result[nranges] counts
+ * the rest.  The remedy is the usual one: repeat those ranges with
+ * zsk_preadv_device, which sizes exactly.  Everything else is the LZ4
+ * contract above; growing a slot's zstd scratch is one of its waits (1).
+ * zsk_preadv_device_indirect stays LZ4-only.
+ */
+ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, unsigned seq_bytes);
 
 /*
  * zsk_preadv_device_async for a range list that is itself in DEVICE memory,

@@ -614,7 +614,8 @@ void CallTable::destroy()
 size_t Slot::device_bytes() const
 {
     return d_comp_cap + d_out_cap + (d_status_cap + d_ck_cap) * 4 +
-           split.frames_cap * 12 + split.items_cap * 8 + zs.frames_cap * 24 + zs.lit_cap + zs.items_cap * 8;
+           split.frames_cap * 12 + split.items_cap * 8 + zs.frames_cap * 24 + zs.lit_cap + zs.items_cap * 8 +
+           zstd_block_scratch_bytes(&zs);
 }
 
 size_t Slot::host_bytes() const
@@ -766,6 +767,8 @@ const char *status_name(int32_t st)
         return "unsupported frame";
     case ST_SEEK_CHECKSUM:
         return "frame checksum mismatch";
+    case ST_SCRATCH:
+        return "ERROR_scratchBounds_tooSmall";
     case ST_NOT_RUN:
         return "decoder did not run";
     default:

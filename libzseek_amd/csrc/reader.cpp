@@ -47,6 +47,7 @@
 #include "lane_plan.h"
 #include "pool.h"
 #include "reader_internal.h"
+#include "zstd_caps.h"
 
 using namespace zsk;
 
@@ -136,6 +137,9 @@ extern "C" ZSEEK_EXPORT zseek_reader_t *zseek_reader_open_full(zseek_read_file_t
     }
     const char *vck = getenv("ZSEEK_VERIFY_CHECKSUMS");
     r->verify = vck && *vck && strcmp(vck, "0") != 0;
+    const char *za = getenv("ZSEEK_ZSTD_ASYNC");
+    if (za && *za && atoi(za) >= 3)
+        r->zstd_async = (unsigned)atoi(za);
     const char *io = getenv("ZSEEK_IO_THREADS");
     if (io && *io && atoi(io) > 1)
         r->io_threads = atoi(io) > 64 ? 64 : atoi(io);
@@ -314,7 +318,7 @@ bool lz4_partial_ok(int32_t st, uint64_t fail_at, uint64_t end_in_frame)
 // zstd1m_block4_*: (0, 524287) succeeds, (0, 524288) fails).
 bool zstd_partial_ok(int32_t st, uint64_t fail_at, uint64_t end_in_frame)
 {
-    if (st == ST_SEEK_CHECKSUM || st == ST_NOT_RUN)
+    if (st == ST_SEEK_CHECKSUM || st == ST_NOT_RUN || st == ST_SCRATCH)
         return false;
     return end_in_frame < fail_at;
 }
@@ -1002,7 +1006,13 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
     if (a.type == ZSEEK_ZSTD) {
         // (a request's few frames are planned on the host from the pinned
         // span -- no plan launch, no synchronization between plan and decode)
-        if ((a.zplan ? zstd_decode_frames_planned(*a.zplan, a.d_plan, a.d_desc, a.n, a.comp, s.d_out, s.d_status,
+        // (the stream-ordered read: no plan on the host and no wait for the
+        // device's; the scratch is reserved there from the batch's bounds)
+        if (a.zasync) {
+            if (zstd_decode_frames_async(a.d_desc, a.n, a.comp, s.d_out, s.d_status, &s.zs, a.q, *a.zasync, d_fail,
+                                         a.stop_last, a.max_dsize) != 0)
+                e = hipErrorLaunchFailure;
+        } else if ((a.zplan ? zstd_decode_frames_planned(*a.zplan, a.d_plan, a.d_desc, a.n, a.comp, s.d_out, s.d_status,
                                                   &s.zs, a.q, d_fail, a.stop_last)
                      : zstd_decode_frames(a.d_desc, a.n, a.comp, s.d_out, s.d_status, &s.zs, a.q, d_fail,
                                           a.stop_last)) != 0)
@@ -1142,12 +1152,55 @@ extern "C" ZSEEK_EXPORT int zsk_dev_lz4_decode_variant(int variant, const zsk_fr
 }
 #endif
 
-// The device API's zstd scratch: a bounded stream-ordered pool (pool.h).
+// The device API's zstd scratch: a bounded stream-ordered pool (pool.h), one
+// for both entries.
+static ScratchPool<ZstdScratch> &zstd_pool()
+{
+    static ScratchPool<ZstdScratch> pool;
+    return pool;
+}
+
+extern "C" ZSEEK_EXPORT void zsk_zstd_bounds_default(uint32_t nframes, uint64_t out_bytes, zsk_zstd_bounds_t *b)
+{
+    if (!b)
+        return;
+    b->out_bytes = out_bytes;
+    zsk::zstd_bounds_default(nframes, out_bytes, &b->max_blocks, &b->max_sequences);
+}
+
+// The stream-ordered entry: the scratch reserved from the caller's bounds, the
+// plan checked against them on the device (zstd_decode_frames_async).
+extern "C" ZSEEK_EXPORT int zsk_zstd_decode_frames_async(const zsk_frame_desc_t *d_desc, uint32_t nframes,
+                                                         const void *d_comp, void *d_out, int32_t *d_status,
+                                                         const zsk_zstd_bounds_t *bounds, void *stream)
+{
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (!bounds)
+        return -1;
+    if (nframes == 0)
+        return 0;
+    // (pooled scratch sized per call, side streams: never in a graph)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(hs, &cap);
+    (void)hipGetLastError();
+    if (ce == hipErrorStreamCaptureImplicit || (ce == hipSuccess && cap != hipStreamCaptureStatusNone))
+        return -1;
+    ScratchPool<ZstdScratch> &pool = zstd_pool();
+    ZstdScratch *s = pool.acquire(hs);
+    if (!s)
+        return -1;
+    const int rc = zsk::zstd_decode_frames_async(reinterpret_cast<const FrameDesc *>(d_desc), nframes,
+                                                 static_cast<const uint8_t *>(d_comp), static_cast<uint8_t *>(d_out),
+                                                 d_status, s, hs, *bounds);
+    pool.release(s, hs);
+    return rc;
+}
+
 extern "C" ZSEEK_EXPORT int zsk_zstd_decode_frames(const zsk_frame_desc_t *d_desc,
                                                    uint32_t nframes, const void *d_comp,
                                                    void *d_out, int32_t *d_status, void *stream)
 {
-    static ScratchPool<ZstdScratch> pool;
+    ScratchPool<ZstdScratch> &pool = zstd_pool();
     hipStream_t hs = static_cast<hipStream_t>(stream);
     ZstdScratch *s = pool.acquire(hs);
     if (!s)
@@ -1243,6 +1296,17 @@ extern "C" ZSEEK_EXPORT bool zsk_reader_set_batch_bytes(zseek_reader_t *reader, 
         return false;
     std::unique_lock<std::shared_mutex> guard(reader->lock);
     reader->batch_bytes = bytes;
+    return true;
+}
+
+// zsk_preadv_device_async on a zstd reader (zseek_hip.h): off, or the decoded
+// bytes per sequence its batches' scratch is sized by.
+extern "C" ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, unsigned seq_bytes)
+{
+    if (!reader || seq_bytes == 1 || seq_bytes == 2)
+        return false;
+    std::unique_lock<std::shared_mutex> guard(reader->lock);
+    reader->zstd_async = seq_bytes;
     return true;
 }
 

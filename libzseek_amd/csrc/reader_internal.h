@@ -57,6 +57,10 @@ struct zseek_reader {
     size_t batch_bytes = 64u << 20;     // decoded bytes per batch
     int io_threads = 1;    // > 1: the caller allows concurrent pread callbacks
     bool verify = false;   // check seek-table frame checksums (the reference never does)
+    // zsk_reader_set_zstd_async: 0 = zsk_preadv_device_async refuses a zstd
+    // reader; >= 3: it decodes each batch with zstd_decode_frames_async, its
+    // sequence bound the batch's decoded bytes / zstd_async
+    unsigned zstd_async = 0;
     std::vector<int> devices;                            // lane i decodes on devices[i]
     std::vector<std::unique_ptr<zsk::DeviceCtx>> lanes;  // created at first use
 };
@@ -120,6 +124,8 @@ struct DecodeBatch {
     // zstd, a few frames planned on the host: the plan and its device copy
     const ZstdHostPlan *zplan = nullptr;
     const uint64_t *d_plan = nullptr;
+    // zstd, the stream-ordered form (zstd_decode_frames_async) by these bounds
+    const ZstdBounds *zasync = nullptr;
     // LZ4 split engine: the host's descriptors, by which the scratch is
     // reserved here (NULL: the caller has reserved it); laid out in order in
     // comp, or scattered (the plan's scan layout); the one-frame route's post

@@ -13,6 +13,7 @@
 #include "range_plan_dev.h"
 #include "range_result.h"
 #include "reader_internal.h"
+#include "zstd_caps.h"
 
 using namespace zsk;
 
@@ -63,6 +64,21 @@ uint64_t fill_desc(const zseek_reader *r, const RangePlan &P, const PlanBatch &b
     return c;
 }
 
+// The bounds an asynchronous zstd batch is decoded by (zsk_reader_set_zstd_async),
+// from the seek table alone: its decoded span (the descriptors pack the frames
+// back to back from 0), a sequence per seq_bytes of it, and per frame two
+// blocks and one per 16 KiB.
+ZstdBounds zstd_async_bounds(const zseek_reader *r, const FrameDesc *desc, size_t n)
+{
+    ZstdBounds B{0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+        B.out_bytes += desc[i].d_size;
+        B.max_blocks += 2 + desc[i].d_size / 16384;
+    }
+    B.max_sequences = B.out_bytes / (r->zstd_async ? r->zstd_async : 3);
+    return B;
+}
+
 // Read, upload, decode and gather batch bi on slot s.  Asynchronous mode
 // (V.async): everything is queued on the caller's stream, directly -- the
 // slot's own stream is not used, so "stream-ordered" needs no event bridge --
@@ -104,7 +120,10 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     const DeviceImage *const img = r->img;
     // behind the packed compressed bytes and their 256-byte read slack: the
     // descriptors, the zstd host plan, the segments, their prefix sum
-    const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames;
+    // (the asynchronous zstd read: no host plan, the device's own plan is
+    // checked against bounds from the seek table -- zstd_async_bounds)
+    const bool zasync = V.async && r->type == ZSEEK_ZSTD;
+    const bool zplan = !img && r->type == ZSEEK_ZSTD && n <= kOneMaxFrames && !zasync;
     const BatchLayout L = vectored_layout(csz, n, nseg, img != nullptr, zplan);
     if (!s.reserve(L.up, pack_at + h_len, h_len, n, ck, V.J.err)) {
         V.J.io_failed = true;
@@ -153,6 +172,9 @@ bool submit_gather(VecJob &V, Slot &s, size_t bi)
     dec.zplan = zplan ? &zp : nullptr;
     dec.d_plan = reinterpret_cast<const uint64_t *>(s.d_comp + L.poff);
     dec.h_desc = h_desc;
+    const ZstdBounds zb = zstd_async_bounds(r, h_desc, n);
+    if (zasync)
+        dec.zasync = &zb;
     if (ck) {
         for (size_t i = 0; i < n; i++)
             s.h_ck[i] = st.checksum[P.frames[b.t0 + i]];
@@ -359,6 +381,8 @@ void grow_idle_for_async(VecJob &V, DeviceCtx &g, size_t table_up, size_t table_
 {
     zseek_reader *r = V.J.r;
     const bool ck = r->verify && r->st.checksum_flag;
+    const bool zstd = r->type == ZSEEK_ZSTD;
+    ZstdBounds zb{0, 0, 0};
     uint64_t up = 0, out = 0, items = 0;
     size_t nmax = 0;
     uint32_t max_dsize;
@@ -367,18 +391,28 @@ void grow_idle_for_async(VecJob &V, DeviceCtx &g, size_t table_up, size_t table_
         const size_t n = b.t1 - b.t0;
         desc.resize(n);
         const uint64_t csz = fill_desc(r, *V.P, b, desc.data(), &max_dsize);
-        // (LZ4 alone: no zstd plan)
+        // (no zstd host plan on this path)
         up = std::max(up, vectored_layout(csz, n, b.s1 - b.s0, r->img != nullptr, false).up);
         out = std::max(out, gather_pack_at(b.d_bytes));
-        items = std::max(items, split_items_needed(desc.data(), (uint32_t)n));
         nmax = std::max(nmax, n);
+        if (zstd) {
+            const ZstdBounds B = zstd_async_bounds(r, desc.data(), n);
+            zb = {std::max(zb.out_bytes, B.out_bytes), std::max(zb.max_blocks, B.max_blocks),
+                  std::max(zb.max_sequences, B.max_sequences)};
+            continue;
+        }
+        items = std::max(items, split_items_needed(desc.data(), (uint32_t)n));
     }
-    const bool split = lz4_pick_engine((uint32_t)nmax) != ENGINE_WAVE;
+    const bool split = !zstd && lz4_pick_engine((uint32_t)nmax) != ENGINE_WAVE;
     char err[ZSEEK_ERRBUF_SIZE];
     for (Slot &s : g.slot) {
         if (s.pending || !nmax)
             continue;
         (void)s.reserve(up, out, 0, nmax, ck, err);
+        if (zstd)
+            (void)zstd_scratch_reserve(&s.zs, (uint32_t)nmax, zb.out_bytes,
+                                       zstd_item_capacity((uint32_t)nmax, zb.max_blocks, zb.max_sequences),
+                                       zb.max_blocks, s.stream);
         // (on the slot's own, idle stream: its wait is no wait; the scratch's
         // first memset is complete before the caller's stream uses it)
         if (split && split_scratch_reserve(&s.split, (uint32_t)nmax, items, s.stream) == 0)
@@ -453,8 +487,9 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *r, void 
     }
     if (refuse_capturing(q, "asynchronous read", errbuf))
         return -1;
-    if (r->type != ZSEEK_LZ4) {
-        // zsk_zstd_decode_frames' plan synchronizes
+    if (r->type != ZSEEK_LZ4 && !(r->type == ZSEEK_ZSTD && r->zstd_async)) {
+        // zsk_zstd_decode_frames' plan synchronizes; the stream-ordered decode
+        // is opt-in, zsk_reader_set_zstd_async
         set_error(errbuf, "asynchronous read: zstd is not supported");
         return -1;
     }

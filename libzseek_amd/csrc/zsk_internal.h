@@ -46,6 +46,7 @@ enum : int32_t {
     ST_TRUNCATED = 102,      // compressed frame ends mid-block
     ST_UNSUPPORTED = 103,
     ST_SEEK_CHECKSUM = 104,  // decoded frame's XXH64 low 32 bits != its seek-table checksum
+    ST_SCRATCH = 105,        // asynchronous zstd decode: the batch did not fit the call's bounds
     ST_NOT_RUN = 0x7fff,     // status slot never written (launch failed)
     ST_BLOCK_ERR = 200,      // internal: block-level parse failure
     ST_DIRECT_FLAG = 0x10000,
@@ -259,6 +260,7 @@ int launch_seq_exec_lit(const FrameDesc *d_desc, uint32_t nframes, const uint8_t
 // zstd decoder (zstd_plan.hip, zstd_decode.hip): plan (item bounds ->
 // rec_base[0..n]) and decode (frame kernel -> items + literal scratch,
 // execute, checksums).  The stage launchers are in zstd_internal.h.
+using ZstdBounds = zsk_zstd_bounds_t;   // the asynchronous decode's bounds (zseek_hip.h)
 struct ZstdScratch {
     uint32_t *bound = nullptr;     // per-frame item bound
     uint32_t *bblk = nullptr;      // per-frame block count (plan)
@@ -275,12 +277,15 @@ struct ZstdScratch {
     uint8_t *hbad = nullptr;       // per Huffman stream: 1 = corrupt
     // [0] item total, [1] output extent, [2] blocks, [3] largest frame (d_size), [4 + k] blk_base
     // at chunk boundary k (zstd_decode.hip: the decode runs in chunks); past
-    // those, zstd_one_kernel's finished-workgroup counter (zero between launches)
+    // those (kDoneWord), zstd_one_kernel's finished-workgroup counter (zero
+    // between launches), then (kFitWord) the asynchronous decode's verdict:
+    // nonzero when the batch did not fit its bounds (zstd_fit_kernel)
     uint64_t *d_total = nullptr;
     uint64_t *total = nullptr;     // pinned host copy of d_total
     hipStream_t side = nullptr;    // the Huffman kernel's stream (beside the sequence replay)
     hipStream_t sq = nullptr;      // the sequence kernel's stream
     static constexpr int kChunks = 8;   // most chunks a decode runs in
+    static constexpr int kDoneWord = 5 + kChunks, kFitWord = 6 + kChunks, kTotalWords = 7 + kChunks;
     hipEvent_t ev_f[kChunks] = {}, ev_s[kChunks] = {}, ev_h[kChunks] = {};   // per chunk: frame / seq / Huffman done
     int side_dev = -1;   // the device the side set belongs to (pooled, zstd_decode.hip)
     uint32_t frames_cap = 0;
@@ -289,6 +294,8 @@ struct ZstdScratch {
 int zstd_scratch_reserve(ZstdScratch *s, uint32_t frames, uint64_t out_bytes, uint64_t items,
                          uint64_t blocks, hipStream_t stream);
 void zstd_scratch_free(ZstdScratch *s);
+// the per-block part of the scratch (table slots, Huffman jobs and their flags, op lists), in bytes
+size_t zstd_block_scratch_bytes(const ZstdScratch *s);
 // Teardown in three steps for an owner with streams of its own: the
 // scratch's memory (after draining its streams; streams and events kept),
 // then its streams, then (zstd_scratch_free) its events -- memory goes while
@@ -306,7 +313,8 @@ int launch_zstd_plan(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d
 // carries a content checksum (a host plan saw them all), no check launch
 int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
                        uint8_t *d_out, int32_t *d_status, ZstdScratch *s, hipStream_t stream,
-                       uint32_t *d_fail_at = nullptr, uint32_t stop_last = 0xFFFFFFFFu, bool cks = true);
+                       uint32_t *d_fail_at = nullptr, uint32_t stop_last = 0xFFFFFFFFu, bool cks = true,
+                       const ZstdBounds *async = nullptr, uint32_t max_dsize = 0xFFFFFFFFu);
 // host_io.hip: a host -> device upload of <= kUploadSmallMax bytes from
 // pinned memory (hipHostMalloc'd, both buffers with >= 15 bytes of slack past
 // `bytes`; h_src_dev its device mapping, hipHostGetDevicePointer) as a kernel
@@ -335,6 +343,20 @@ int download_flagged(uint32_t *h_status, void *h_status_dev, const uint32_t *d_s
 int zstd_decode_frames(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
                        uint8_t *d_out, int32_t *d_status, ZstdScratch *s, hipStream_t stream,
                        uint32_t *d_fail_at = nullptr, uint32_t stop_last = 0xFFFFFFFFu);
+// The stream-ordered form: no wait for the plan.  The scratch is reserved from
+// the bounds (item capacity: zstd_caps.h) before anything is queued -- the one
+// host wait, when it has to grow -- and the device checks its plan against them
+// (zstd_fit_kernel): a batch that does not fit gets ST_SCRATCH in every status
+// and writes nothing else.  max_dsize: a host-known bound of the largest
+// d_size (0xFFFFFFFF: unknown).
+int zstd_decode_frames_async(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, uint8_t *d_out,
+                             int32_t *d_status, ZstdScratch *s, hipStream_t stream, const ZstdBounds &B,
+                             uint32_t *d_fail_at = nullptr, uint32_t stop_last = 0xFFFFFFFFu,
+                             uint32_t max_dsize = 0xFFFFFFFFu);
+// ... its plan launches (zstd_plan.hip): plan, scan, then the verdict and the
+// chunk boundaries into d_total; nothing comes back to the host
+int launch_zstd_plan_async(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, ZstdScratch *s,
+                           int32_t *d_status, uint64_t items_cap, const ZstdBounds &B, hipStream_t stream);
 // The same for a request's few frames whose compressed bytes are also in host
 // memory (h_desc / h_comp: the reader's pinned upload, the same layout as
 // d_desc / d_comp): the plan -- zstd_plan_kernel's per-frame bounds

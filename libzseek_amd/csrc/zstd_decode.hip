@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "xxh64_dev.h"
+#include "zstd_caps.h"
 #include "zstd_dev.h"
 #include "zstd_internal.h"
 
@@ -33,13 +34,25 @@ using namespace xxh64d;
 __global__ __launch_bounds__(256) void zstd_check_kernel(
     const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ out,
     const uint64_t *__restrict__ ck, const uint8_t *__restrict__ ops, const uint64_t *__restrict__ blk_base,
-    int32_t *__restrict__ status, uint32_t *__restrict__ fail_at, uint32_t stop_last, uint32_t f0)
+    int32_t *__restrict__ status, uint32_t *__restrict__ fail_at, uint32_t stop_last, uint32_t f0,
+    const uint64_t *__restrict__ fit)
 {
     __shared__ uint64_t buf[4][128];
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t f = uni(blockIdx.x * 4 + w);   // frames [f0, f0 + n) of the batch
     if (f >= n)
         return;
+    // the asynchronous decode, a batch that did not fit its bounds: the
+    // call's last kernel names the refusal (zstd_fit_kernel left ST_NOT_RUN,
+    // at which the execute kernels return at their top)
+    if (fit && *fit) {
+        if (lane == 0) {
+            status[f] = ST_SCRATCH;
+            if (fail_at)
+                fail_at[f] = 0;
+        }
+        return;
+    }
     if (!(ck[f] >> 63) || uni((uint32_t)status[f]) != (uint32_t)ST_OK)
         return;
     const FrameDesc d = desc[f];
@@ -222,8 +235,8 @@ int zstd_scratch_reserve(ZstdScratch *s, uint32_t frames, uint64_t out_bytes, ui
             hipMalloc((void **)&s->nitems, sizeof(uint32_t) * cap) != hipSuccess ||
             hipMalloc((void **)&s->ck, sizeof(uint64_t) * cap) != hipSuccess ||
             hipMalloc((void **)&s->stop, sizeof(uint32_t) * cap) != hipSuccess ||
-            hipMalloc((void **)&s->d_total, (6 + ZstdScratch::kChunks) * sizeof(uint64_t)) != hipSuccess ||
-            hipMemset(s->d_total, 0, (6 + ZstdScratch::kChunks) * sizeof(uint64_t)) != hipSuccess ||
+            hipMalloc((void **)&s->d_total, ZstdScratch::kTotalWords * sizeof(uint64_t)) != hipSuccess ||
+            hipMemset(s->d_total, 0, ZstdScratch::kTotalWords * sizeof(uint64_t)) != hipSuccess ||
             hipHostMalloc((void **)&s->total, (5 + ZstdScratch::kChunks) * sizeof(uint64_t), hipHostMallocDefault) !=
                 hipSuccess)
             return -1;
@@ -241,6 +254,11 @@ int zstd_scratch_reserve(ZstdScratch *s, uint32_t frames, uint64_t out_bytes, ui
     }
     // op lists: 4 per block + 4 per frame
     return grow(&s->ops, s->ops_cap, blocks + frames, 4 * sizeof(ZOp));
+}
+
+size_t zstd_block_scratch_bytes(const ZstdScratch *s)
+{
+    return s->blocks_cap * (kZSlot + 4 * sizeof(HufJob) + 4) + s->ops_cap * 4 * sizeof(ZOp);
 }
 
 void zstd_scratch_release_memory(ZstdScratch *s)
@@ -278,14 +296,25 @@ void zstd_scratch_free(ZstdScratch *s)
 // each chunk's fix-up, execute and checksums once its sequence (s->sq) and
 // Huffman (s->side) kernels are done; those start on a chunk as soon as its
 // frame kernel is.  s must hold the last plan of these frames.
+// async (the stream-ordered form): the plan's totals never reach the host.
+// Every chunk's Huffman grid covers the call's block capacity and takes its
+// job range from d_total, every chunk is treated as having Huffman blocks,
+// the checksum kernel always runs, the largest frame is max_dsize, and each
+// stage returns at its top when zstd_fit_kernel's verdict says the batch did
+// not fit.
 int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp,
                        uint8_t *d_out, int32_t *d_status, ZstdScratch *s, hipStream_t stream,
-                       uint32_t *d_fail_at, uint32_t stop_last, bool cks)
+                       uint32_t *d_fail_at, uint32_t stop_last, bool cks, const ZstdBounds *async,
+                       uint32_t max_dsize)
 {
     if (nframes == 0)
         return 0;
-    if (s->total[2] > s->blocks_cap)
+    if (async ? async->max_blocks > s->blocks_cap : s->total[2] > s->blocks_cap)
         return -1;
+    if (async)
+        cks = true;
+    else
+        max_dsize = (uint32_t)std::min<uint64_t>(s->total[3], 0xFFFFFFFFu);
     const uint32_t K = zstd_chunks(nframes);
     static const bool serial = getenv("ZSEEK_ZSTD_SERIAL") != nullptr;   // diagnostics: one stream
     // the one-frame route (a request's few frames): the execute a workgroup
@@ -299,7 +328,8 @@ int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
     static const bool fuse_off = env_is_zero("ZSEEK_ONE_FUSE");
     const bool fuse = one && !fuse_off;
     hipStream_t const hs = serial ? stream : s->side, qs = serial || one ? stream : s->sq;
-    const ZstdCall C{d_desc, d_comp, d_status, d_fail_at};
+    const uint64_t *const fit = async ? s->d_total + ZstdScratch::kFitWord : nullptr;
+    const ZstdCall C{d_desc, d_comp, d_status, d_fail_at, fit};
     auto drain = [&] {   // an enqueue failed: nothing may still write the scratch
         (void)hipStreamSynchronize(stream);
         (void)hipStreamSynchronize(s->side);
@@ -307,8 +337,10 @@ int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
         return -1;
     };
     auto chunk = [&](uint32_t c) {
-        return ZstdChunk{c, (uint32_t)((uint64_t)nframes * c / K), (uint32_t)((uint64_t)nframes * (c + 1) / K),
-                         s->total[4 + c], s->total[5 + c]};
+        const uint32_t f0 = (uint32_t)((uint64_t)nframes * c / K), f1 = (uint32_t)((uint64_t)nframes * (c + 1) / K);
+        if (async)
+            return ZstdChunk{c, f0, f1, 0, async->max_blocks, s->d_total + 4 + c};
+        return ZstdChunk{c, f0, f1, s->total[4 + c], s->total[5 + c], nullptr};
     };
     for (uint32_t c = 0; c < K; c++) {
         const ZstdChunk ch = chunk(c);
@@ -359,14 +391,13 @@ int launch_zstd_decode(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
         hipEvent_t tx = kernel_span_begin(stream);
         const uint32_t stop = c + 1 == K ? stop_last : 0xFFFFFFFFu;   // (the batch's last frame)
         if (launch_seq_exec_lit(d_desc + f0, m, s->lit, d_out, s->rec_base + f0, s->items, s->nitems + f0,
-                                d_status + f0, stream, one, (uint32_t)std::min<uint64_t>(s->total[3], 0xFFFFFFFFu),
-                                stop) != 0)
+                                d_status + f0, stream, one, max_dsize, stop) != 0)
             rc = -1;
         kernel_span_end(SPAN_ZEXEC, tx, stream);
         if (cks)   // (a host plan that met no content checksum: nothing to check)
             hipLaunchKernelGGL(zstd_check_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, d_desc + f0, m, d_out,
                                s->ck + f0, s->ops, s->blk_base, d_status + f0,
-                               d_fail_at ? d_fail_at + f0 : nullptr, stop, f0);
+                               d_fail_at ? d_fail_at + f0 : nullptr, stop, f0, fit);
     }
     stage_mark(3, stream);
     stage_mark(4, stream);
@@ -394,6 +425,29 @@ int zstd_decode_frames(const FrameDesc *d_desc, uint32_t nframes, const uint8_t 
     if (zstd_scratch_reserve(s, nframes, s->total[1], s->total[0], s->total[2], stream) != 0)
         return -1;
     return launch_zstd_decode(d_desc, nframes, d_comp, d_out, d_status, s, stream, d_fail_at, stop_last);
+}
+
+// The stream-ordered form: reserve from the bounds (the only host wait: a
+// scratch that has to grow), plan, verdict, decode -- nothing comes back.
+int zstd_decode_frames_async(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, uint8_t *d_out,
+                             int32_t *d_status, ZstdScratch *s, hipStream_t stream, const ZstdBounds &B,
+                             uint32_t *d_fail_at, uint32_t stop_last, uint32_t max_dsize)
+{
+    if (nframes == 0)
+        return 0;
+    (void)hipGetLastError();   // a stale error of an earlier call is not this launch's
+    const uint64_t items = zstd_item_capacity(nframes, B.max_blocks, B.max_sequences);
+    // (4 * max_blocks Huffman jobs a grid; bounds past that are no scratch a device holds)
+    if (items == ~0ull || B.max_blocks >= (1ull << 29) || B.out_bytes >= (1ull << 58))
+        return -1;
+    if (zstd_scratch_reserve(s, nframes, B.out_bytes, items, B.max_blocks, stream) != 0)
+        return -1;
+    stage_mark(0, stream);
+    if (launch_zstd_plan_async(d_desc, nframes, d_comp, s, d_status, items, B, stream) != 0)
+        return -1;
+    stage_mark(1, stream);
+    return launch_zstd_decode(d_desc, nframes, d_comp, d_out, d_status, s, stream, d_fail_at, stop_last, true, &B,
+                              max_dsize);
 }
 
 int zstd_decode_frames_planned(const ZstdHostPlan &P, const uint64_t *d_plan, const FrameDesc *d_desc,

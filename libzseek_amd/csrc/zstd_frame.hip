@@ -582,11 +582,15 @@ __global__ __launch_bounds__(64 * kZW) __attribute__((amdgpu_waves_per_eu(4))) v
     const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ comp,
     uint8_t *__restrict__ lit, uint64_t lit_cap, const uint64_t *__restrict__ rec_base,
     uint64_t capacity, const uint64_t *__restrict__ blk_base, uint8_t *__restrict__ ops,
-    uint8_t *__restrict__ slots, uint8_t *__restrict__ jobs, uint32_t f0)
+    uint8_t *__restrict__ slots, uint8_t *__restrict__ jobs, uint32_t f0, const uint64_t *__restrict__ fit)
 {
     static_assert(kZW >= 2, "the helper wave needs a second ZLds");
     __shared__ ZLds lds[kZW];
     __shared__ HelpBox box;
+    // (the asynchronous decode: a batch that did not fit its bounds; the
+    // whole workgroup, before any barrier)
+    if (fit && *fit)
+        return;
     ZF_T0(tk)
     const uint32_t w = threadIdx.x >> 6;
     const uint32_t f = HELP ? uni(f0 + blockIdx.x) : uni(f0 + blockIdx.x * kZW + w);   // frames [f0, n)
@@ -681,7 +685,7 @@ void launch_zstd_frame(const ZstdCall &C, ZstdScratch *s, const ZstdChunk &c, bo
     const uint32_t m = c.f1 - c.f0;
     const auto go = [&](auto kernel, uint32_t groups) {
         hipLaunchKernelGGL(kernel, dim3(groups), dim3(64 * kZW), 0, stream, C.desc, c.f1, C.comp, s->lit, s->lit_cap,
-                           s->rec_base, s->items_cap, s->blk_base, s->ops, s->slots, s->hjobs, c.f0);
+                           s->rec_base, s->items_cap, s->blk_base, s->ops, s->slots, s->hjobs, c.f0, C.fit);
     };
     if (help && !help_off)
         go(zstd_frame_kernel<true>, m);

@@ -29,11 +29,23 @@ using namespace lz4d;
 template <int DIAG, int B = 4>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void zstd_huf_kernel(
     const uint8_t *__restrict__ jobs, uint32_t nj, const uint8_t *__restrict__ comp,
-    const uint8_t *__restrict__ slots, uint8_t *__restrict__ lit, uint8_t *__restrict__ hbad)
+    const uint8_t *__restrict__ slots, uint8_t *__restrict__ lit, uint8_t *__restrict__ hbad,
+    const uint64_t *__restrict__ jr)
 {
     __shared__ __attribute__((aligned(16))) uint16_t tabs[kHufLdsCells];
     __shared__ __attribute__((aligned(16))) uint8_t rings[kRS * 1024];
     const uint32_t lane = threadIdx.x;
+    if (jr) {
+        // the asynchronous decode: the grid covers the call's block capacity,
+        // jobs / hbad are the arrays' starts and the chunk's blocks are
+        // [jr[0], jr[1]) in device memory; a surplus workgroup leaves here
+        const uint64_t b0 = jr[0];
+        nj = (uint32_t)(4 * (jr[1] - b0));
+        if (blockIdx.x * 64 >= nj)
+            return;
+        jobs += 4 * b0 * sizeof(HufJob);
+        hbad += 4 * b0;
+    }
     const uint32_t j = blockIdx.x * 64 + lane;
     HufJob J = {0, 0, 0, 0, 0, 0};
     if (j < nj)
@@ -120,9 +132,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void zs
 
 __global__ __launch_bounds__(kHufOneT) void zstd_huf_one_kernel(
     const uint8_t *__restrict__ jobs, const uint8_t *__restrict__ comp, const uint8_t *__restrict__ slots,
-    uint8_t *__restrict__ lit, uint8_t *__restrict__ hbad)
+    uint8_t *__restrict__ lit, uint8_t *__restrict__ hbad, const uint64_t *__restrict__ jr)
 {
     __shared__ HufOneLds H;
+    if (jr) {   // (the asynchronous decode, as in zstd_huf_kernel)
+        const uint64_t b0 = jr[0];
+        if (blockIdx.x >= 4 * (jr[1] - b0))
+            return;
+        jobs += 4 * b0 * sizeof(HufJob);
+        hbad += 4 * b0;
+    }
     huf_one_body(H, blockIdx.x, threadIdx.x, jobs, comp, slots, lit, hbad);
 }
 
@@ -132,9 +151,12 @@ __global__ __launch_bounds__(64) void zstd_seq_kernel(
     uint8_t *__restrict__ ops, const uint64_t *__restrict__ blk_base,
     const uint8_t *__restrict__ slots, uint32_t *__restrict__ stop,
     const uint64_t *__restrict__ rec_base, uint64_t *__restrict__ items, uint32_t *__restrict__ nitems,
-    int32_t *__restrict__ status, uint64_t *__restrict__ ck, uint32_t *__restrict__ fail_at, uint32_t f0)
+    int32_t *__restrict__ status, uint64_t *__restrict__ ck, uint32_t *__restrict__ fail_at, uint32_t f0,
+    const uint64_t *__restrict__ fit)
 {
     __shared__ SeqLds<LANES, CELLS, ONE> SH;
+    if (fit && *fit)   // (the asynchronous decode: the batch did not fit its bounds)
+        return;
     seq_body<LANES, CELLS, GM, ONE>(SH, blockIdx.x, desc, n, comp, ops, blk_base, slots, stop, rec_base, items,
                                     nitems, status, ck, fail_at, f0);
 }
@@ -154,7 +176,7 @@ __global__ __launch_bounds__(kHufOneT) void zstd_one_kernel(
     const uint64_t *__restrict__ rec_base, uint64_t *__restrict__ items, uint32_t *__restrict__ nitems,
     int32_t *__restrict__ status, uint64_t *__restrict__ ck, uint32_t *__restrict__ fail_at, uint32_t f0,
     uint32_t m, const uint8_t *__restrict__ jobs, uint8_t *__restrict__ lit, uint8_t *__restrict__ hbad,
-    uint32_t *__restrict__ done)
+    uint32_t *__restrict__ done, const uint64_t *__restrict__ fit, const uint64_t *__restrict__ jr)
 {
     __shared__ union {
         SeqLds<1, 0, true> s;
@@ -162,6 +184,21 @@ __global__ __launch_bounds__(kHufOneT) void zstd_one_kernel(
     } U;
     __shared__ uint32_t last;
     const uint32_t b = blockIdx.x, t = threadIdx.x;
+    // the workgroups that take part (and count in `done`): the whole grid, or
+    // for the asynchronous decode, whose grid covers the call's block
+    // capacity, the m replays and the chunk's jobs (blocks [jr[0], jr[1]) in
+    // device memory; none at all when the batch did not fit its bounds)
+    uint32_t parts = gridDim.x;
+    if (jr) {
+        if (*fit)
+            return;
+        const uint64_t b0 = jr[0];
+        parts = m + (uint32_t)(4 * (jr[1] - b0));
+        if (b >= parts)
+            return;
+        jobs += 4 * b0 * sizeof(HufJob);
+        hbad += 4 * b0;
+    }
     if (b < m) {
         // waves 0 and 1: the replay's chain and its vector phase.  Waves 2
         // and 3 leave before any barrier: a wave that has ended no longer
@@ -179,7 +216,7 @@ __global__ __launch_bounds__(kHufOneT) void zstd_one_kernel(
     __syncthreads();
     if (t == 0) {
         __threadfence();
-        last = atomicAdd(done, 1u) == gridDim.x - 1 ? 1u : 0u;
+        last = atomicAdd(done, 1u) == parts - 1 ? 1u : 0u;
     }
     __syncthreads();
     if (!last)
@@ -195,9 +232,11 @@ __global__ __launch_bounds__(kHufOneT) void zstd_one_kernel(
 __global__ __launch_bounds__(256) void zstd_lit_fix_kernel(
     uint32_t n, const uint8_t *__restrict__ ops, const uint64_t *__restrict__ blk_base,
     const uint8_t *__restrict__ hbad, const uint32_t *__restrict__ stop, int32_t *__restrict__ status,
-    uint32_t *__restrict__ nitems, uint32_t *__restrict__ fail_at, uint32_t f0)
+    uint32_t *__restrict__ nitems, uint32_t *__restrict__ fail_at, uint32_t f0, const uint64_t *__restrict__ fit)
 {
     const uint32_t f = f0 + blockIdx.x * 256 + threadIdx.x;   // frames [f0, n)
+    if (fit && *fit)   // (the asynchronous decode: the batch did not fit its bounds)
+        return;
     if (f < n)
         lit_fix(f, ops, blk_base, hbad, stop, status, nitems, fail_at);
 }
@@ -225,14 +264,18 @@ void zstd_seq_timers(hipStream_t stream)
 
 void launch_zstd_huf(const ZstdCall &C, ZstdScratch *s, const ZstdChunk &c, bool one, hipStream_t stream)
 {
+    // (c.dev: b0 = 0 and b1 the block capacity, so jb / hb are the arrays'
+    // starts and nj sizes the grid; the kernels take the true range from c.dev)
     const uint32_t nj = (uint32_t)(4 * (c.b1 - c.b0));
     const uint8_t *jb = s->hjobs + 4 * c.b0 * sizeof(HufJob);
     uint8_t *hb = s->hbad + 4 * c.b0;
     const auto go_one = [&] {
-        hipLaunchKernelGGL(zstd_huf_one_kernel, dim3(nj), dim3(kHufOneT), 0, stream, jb, C.comp, s->slots, s->lit, hb);
+        hipLaunchKernelGGL(zstd_huf_one_kernel, dim3(nj), dim3(kHufOneT), 0, stream, jb, C.comp, s->slots, s->lit, hb,
+                           c.dev);
     };
     const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((nj + 63) / 64), dim3(64), 0, stream, jb, nj, C.comp, s->slots, s->lit, hb);
+        hipLaunchKernelGGL(kernel, dim3((nj + 63) / 64), dim3(64), 0, stream, jb, nj, C.comp, s->slots, s->lit, hb,
+                           c.dev);
     };
 #ifdef ZSK_TUNING
     // diagnostics (tuning builds, ZSEEK_ZSTD_HUF_DIAG): 1 / 3 / 7 / 8
@@ -273,7 +316,8 @@ void launch_zstd_seq(const ZstdCall &C, ZstdScratch *s, const ZstdChunk &c, bool
     const uint32_t m = c.f1 - c.f0;
     const auto go = [&](auto kernel, uint32_t groups) {
         hipLaunchKernelGGL(kernel, dim3(groups), dim3(64), 0, stream, C.desc, c.f1, C.comp, s->ops, s->blk_base,
-                           s->slots, s->stop, s->rec_base, s->items, s->nitems, C.status, s->ck, C.fail_at, c.f0);
+                           s->slots, s->stop, s->rec_base, s->items, s->nitems, C.status, s->ck, C.fail_at, c.f0,
+                           C.fit);
     };
     if (one) {
         go(zstd_seq_kernel<1, 0, 0, true>, m);
@@ -289,13 +333,13 @@ void launch_zstd_one(const ZstdCall &C, ZstdScratch *s, const ZstdChunk &c, hipS
     hipLaunchKernelGGL(zstd_one_kernel, dim3(m + nj), dim3(kHufOneT), 0, stream, C.desc, c.f1, C.comp, s->ops,
                        s->blk_base, s->slots, s->stop, s->rec_base, s->items, s->nitems, C.status, s->ck, C.fail_at,
                        c.f0, m, s->hjobs + 4 * c.b0 * sizeof(HufJob), s->lit, s->hbad + 4 * c.b0,
-                       reinterpret_cast<uint32_t *>(s->d_total + 5 + ZstdScratch::kChunks));
+                       reinterpret_cast<uint32_t *>(s->d_total + ZstdScratch::kDoneWord), C.fit, c.dev);
 }
 
 void launch_zstd_lit_fix(const ZstdCall &C, ZstdScratch *s, const ZstdChunk &c, hipStream_t stream)
 {
     hipLaunchKernelGGL(zstd_lit_fix_kernel, dim3((c.f1 - c.f0 + 255) / 256), dim3(256), 0, stream, c.f1, s->ops,
-                       s->blk_base, s->hbad, s->stop, C.status, s->nitems, C.fail_at, c.f0);
+                       s->blk_base, s->hbad, s->stop, C.status, s->nitems, C.fail_at, c.f0, C.fit);
 }
 
 }   // namespace zsk

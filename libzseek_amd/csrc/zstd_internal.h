@@ -17,6 +17,10 @@ struct ZstdCall {
     const uint8_t *comp;
     int32_t *status;
     uint32_t *fail_at;   // optional
+    // the asynchronous decode (zstd_decode_frames_async): the device word that
+    // is nonzero when the batch did not fit the call's bounds -- every stage
+    // then returns at its top.  Null: the host sized the scratch from the plan
+    const uint64_t *fit = nullptr;
 };
 
 // a chunk of the call: frames [f0, f1) and their block slots [b0, b1)
@@ -24,6 +28,10 @@ struct ZstdChunk {
     uint32_t c;   // its index (events, diagnostics)
     uint32_t f0, f1;
     uint64_t b0, b1;
+    // the asynchronous decode: the host has no plan totals, [b0, b1) is [0,
+    // the call's block capacity) and sizes the Huffman grids; the kernels take
+    // the chunk's true range from these two device words (d_total[4 + c])
+    const uint64_t *dev = nullptr;
 };
 
 // chunks a decode of n frames runs in (zstd_decode.hip)

@@ -19,6 +19,7 @@ struct ZstdFramePlan {
     uint32_t bound;    // item slots: 8 + 4 per block + 2 per sequence + the pairs' padding, rounded up to 4
     uint32_t blocks;   // block headers met
     bool cks;          // some frame carries a content checksum (the check kernel runs)
+    uint64_t sequences;   // sequences the sequence sections declare (zstd_caps.h's bound counts them)
 };
 
 // B(p): byte p of the entry's clen bytes, 0 for p >= clen.  Walks skippable
@@ -28,7 +29,7 @@ template <class ByteAt>
 ZSK_HD ZstdFramePlan zstd_frame_plan(ByteAt B, uint32_t clen)
 {
     constexpr uint32_t kMagic = 0xFD2FB528u, kSkippable = 0x184D2A50u;
-    uint64_t items = 8;
+    uint64_t items = 8, sequences = 0;
     uint32_t ip = 0, blocks = 0;
     bool cks = false;
     while (clen - ip >= 9 && items < (1u << 30)) {
@@ -69,6 +70,7 @@ ZSK_HD ZstdFramePlan zstd_frame_plan(ByteAt B, uint32_t clen)
                     const uint32_t nseq = s0 < 128 ? s0 : s0 < 255 ? ((s0 - 128) << 8) + B(q + 1)
                                                                    : (B(q + 1) | B(q + 2) << 8) + 0x7F00;
                     items += 2ull * nseq + (2ull * nseq + 62) / 63;
+                    sequences += nseq;
                 }
             }
             ip += type == 1 ? 1 : bsize;
@@ -82,7 +84,7 @@ ZSK_HD ZstdFramePlan zstd_frame_plan(ByteAt B, uint32_t clen)
             cks = true;
         }
     }
-    return ZstdFramePlan{(uint32_t)((items + 3) & ~3ull), blocks, cks};
+    return ZstdFramePlan{(uint32_t)((items + 3) & ~3ull), blocks, cks, sequences};
 }
 
 }   // namespace zsk

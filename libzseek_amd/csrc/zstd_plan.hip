@@ -139,7 +139,54 @@ __global__ void zstd_bounds_kernel(const uint64_t *__restrict__ blk_base, uint32
         out[c] = blk_base[(uint64_t)n * c / k];
 }
 
+// The asynchronous decode's verdict, behind the scan (a thread per frame; every
+// thread reads the three totals, wave-uniform): the batch fits when its item
+// total, block total and output extent are within what the host reserved.
+// Then zstd_bounds_kernel's chunk boundaries, else boundaries of 0 (no Huffman
+// job anywhere), the verdict word set and every status ST_NOT_RUN, at which
+// the execute kernels return at their top; zstd_check_kernel, the call's last,
+// turns it into ST_SCRATCH.  (total[0..2] are only read here, total[4..] and
+// the verdict only written.)
+__global__ __launch_bounds__(256) void zstd_fit_kernel(
+    const uint64_t *__restrict__ blk_base, uint32_t n, uint32_t k, uint64_t *total, uint64_t items_cap,
+    uint64_t max_blocks, uint64_t out_bytes, int32_t *__restrict__ status)
+{
+    const uint32_t f = blockIdx.x * 256 + threadIdx.x;
+    const bool fits = total[0] <= items_cap && total[2] <= max_blocks && total[1] <= out_bytes;
+    if (f <= k)
+        total[4 + f] = fits ? blk_base[(uint64_t)n * f / k] : 0;
+    if (f == 0)
+        total[ZstdScratch::kFitWord] = fits ? 0 : 1;
+    if (!fits && f < n)
+        status[f] = ST_NOT_RUN;
+}
+
+int plan_kernels(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, ZstdScratch *s,
+                 hipStream_t stream)
+{
+    if (hipMemsetAsync(s->d_total, 0, 4 * sizeof(uint64_t), stream) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(zstd_plan_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, d_desc,
+                       nframes, d_comp, s->bound, s->bblk, reinterpret_cast<unsigned long long *>(s->d_total + 1));
+    hipLaunchKernelGGL(zstd_scan_kernel, dim3(1), dim3(1024), 0, stream, s->bound, s->bblk, nframes,
+                       s->rec_base, s->blk_base, s->d_total);
+    return 0;
+}
+
 }   // namespace
+
+int launch_zstd_plan_async(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, ZstdScratch *s,
+                           int32_t *d_status, uint64_t items_cap, const ZstdBounds &B, hipStream_t stream)
+{
+    if (nframes == 0)
+        return 0;
+    if (plan_kernels(d_desc, nframes, d_comp, s, stream) != 0)
+        return -1;
+    // (a grid of at least kChunks + 1 threads: the boundaries)
+    hipLaunchKernelGGL(zstd_fit_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, s->blk_base, nframes,
+                       zstd_chunks(nframes), s->d_total, items_cap, B.max_blocks, B.out_bytes, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 // Plan only: bounds + offsets, then the item total, output extent and block
 // total copied into s->total (pinned host memory), valid once the stream
@@ -149,12 +196,8 @@ int launch_zstd_plan(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d
 {
     if (nframes == 0)
         return 0;
-    if (hipMemsetAsync(s->d_total, 0, 4 * sizeof(uint64_t), stream) != hipSuccess)
+    if (plan_kernels(d_desc, nframes, d_comp, s, stream) != 0)
         return -1;
-    hipLaunchKernelGGL(zstd_plan_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, d_desc,
-                       nframes, d_comp, s->bound, s->bblk, reinterpret_cast<unsigned long long *>(s->d_total + 1));
-    hipLaunchKernelGGL(zstd_scan_kernel, dim3(1), dim3(1024), 0, stream, s->bound, s->bblk, nframes,
-                       s->rec_base, s->blk_base, s->d_total);
     const uint32_t k = zstd_chunks(nframes);
     hipLaunchKernelGGL(zstd_bounds_kernel, dim3(1), dim3(64), 0, stream, s->blk_base, nframes, k, s->d_total + 4);
     if (hipGetLastError() != hipSuccess)

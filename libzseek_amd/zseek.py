@@ -26,6 +26,7 @@ ERRBUF = 80
 ZSEEK_ZSTD, ZSEEK_LZ4 = 0, 1
 ZSK_OK = 0
 ZSK_ERR_SEEK_CHECKSUM = 104
+ERR_SCRATCH = 105   # ZSK_ERR_SCRATCH: an asynchronous zstd batch did not fit its bounds
 
 WRITE_FN = C.CFUNCTYPE(C.c_bool, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 PREAD_FN = C.CFUNCTYPE(C.c_ssize_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p)
@@ -75,6 +76,11 @@ class WriterStatsC(C.Structure):
                                           "compressed_size", "buffer_size")]
 
 
+class ZstdBoundsC(C.Structure):
+    """zsk_zstd_bounds_t"""
+    _fields_ = [("out_bytes", C.c_uint64), ("max_blocks", C.c_uint64), ("max_sequences", C.c_uint64)]
+
+
 class GpuStatsC(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("frames_decoded", C.c_uint64),
                 ("bytes_decoded", C.c_uint64), ("bytes_uploaded", C.c_uint64),
@@ -122,6 +128,7 @@ EXPORTED = [
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
     "zsk_zstd_compress_scratch_size", "zsk_zstd_compress_frames", "zsk_zstd_image_bound", "zsk_zstd_build_image",
     "zsk_zstd_compress_scratch_size_ex", "zsk_zstd_compress_frames_ex",
+    "zsk_zstd_bounds_default", "zsk_zstd_decode_frames_async", "zsk_reader_set_zstd_async",
 ]
 
 _lib = None
@@ -163,6 +170,13 @@ def lib() -> C.CDLL:
     L.zsk_zstd_decode_frames.restype = C.c_int
     L.zsk_zstd_decode_frames.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+    L.zsk_zstd_bounds_default.restype = None
+    L.zsk_zstd_bounds_default.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(ZstdBoundsC)]
+    L.zsk_zstd_decode_frames_async.restype = C.c_int
+    L.zsk_zstd_decode_frames_async.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(ZstdBoundsC), C.c_void_p]
+    L.zsk_reader_set_zstd_async.restype = C.c_bool
+    L.zsk_reader_set_zstd_async.argtypes = [C.c_void_p, C.c_uint]
     L.zsk_lz4_decode_frames_ex.restype = C.c_int
     L.zsk_lz4_decode_frames_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int]
@@ -659,6 +673,12 @@ class Reader:
         """zsk_reader_set_verify_checksums: check seek-table frame checksums."""
         lib().zsk_reader_set_verify_checksums(self._h, bool(on))
 
+    def set_zstd_async(self, seq_bytes: int) -> bool:
+        """zsk_reader_set_zstd_async: preadv_device_async on a zstd reader, its
+        scratch sized at a sequence per seq_bytes decoded bytes (0: off; 1 and
+        2: refused, False)."""
+        return bool(lib().zsk_reader_set_zstd_async(self._h, seq_bytes))
+
     def close(self) -> None:
         if self._h:
             lib().zseek_reader_close(self._h, None, self._err)
@@ -757,6 +777,38 @@ def zstd_decode_frames(desc, comp, out, status, stream: int | None = None) -> No
                                       status.data_ptr(), stream)
     if rc != 0:
         raise ZseekError("zsk_zstd_decode_frames launch failed")
+
+
+def zstd_bounds_default(nframes: int, out_bytes: int) -> dict:
+    """zsk_zstd_bounds_default: the default bounds of an asynchronous decode of
+    nframes entries into out_bytes, as zstd_decode_frames_async takes them."""
+    b = ZstdBoundsC()
+    lib().zsk_zstd_bounds_default(nframes, out_bytes, C.byref(b))
+    return {"out_bytes": b.out_bytes, "max_blocks": b.max_blocks, "max_sequences": b.max_sequences}
+
+
+def zstd_decode_frames_async(desc, comp, out, status, bounds: dict | None = None,
+                             stream: int | None = None) -> None:
+    """zsk_zstd_decode_frames_async on torch device tensors (the layout of
+    zstd_decode_frames): queued on the stream, no wait for its plan.  bounds:
+    out_bytes / max_blocks / max_sequences (None: zstd_bounds_default for
+    out's size); a batch beyond them leaves ERR_SCRATCH in every status."""
+    import torch
+    n = status.numel()
+    if desc.numel() != n * 24:
+        raise ValueError("desc must hold 24 bytes per frame")
+    for t in (desc, comp, out, status):
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("zstd_decode_frames_async needs contiguous device tensors")
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    if bounds is None:
+        bounds = zstd_bounds_default(n, out.numel())
+    b = ZstdBoundsC(bounds["out_bytes"], bounds["max_blocks"], bounds["max_sequences"])
+    rc = lib().zsk_zstd_decode_frames_async(desc.data_ptr(), n, comp.data_ptr(), out.data_ptr(),
+                                            status.data_ptr(), C.byref(b), stream)
+    if rc != 0:
+        raise ZseekError("zsk_zstd_decode_frames_async launch failed")
 
 
 def verify_frame_checksums(desc, out, checksums, status, stream: int | None = None) -> None:
