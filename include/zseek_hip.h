@@ -31,7 +31,12 @@
  *                            (a zstd reader: after zsk_reader_set_zstd_async).
  *   zsk_preadv_device_indirect — ... with the range list in device memory
  *                            too, planned by kernels from the seek table a
- *                            device-image reader keeps resident.
+ *                            device-image reader keeps resident (a zstd
+ *                            reader: after zsk_reader_zstd_census).
+ *   zsk_reader_zstd_census — no reference function: the largest scratch need
+ *                            of any one entry of a zstd file in device
+ *                            memory, from one walk over the whole file; what
+ *                            bounds the device-planned read's zstd scratch.
  *   zsk_verify_frame_checksums — the seek table's per-frame checksum,
  *                            parsed by seek_table.c:95-97 and never checked
  *                            there, checked on the GPU.
@@ -366,13 +371,15 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device_async(zseek_reader_t *reader, void *d_buf
  * the rest.  The remedy is the usual one: repeat those ranges with
  * zsk_preadv_device, which sizes exactly.  Everything else is the LZ4
  * contract above; growing a slot's zstd scratch is one of its waits (1).
- * zsk_preadv_device_indirect stays LZ4-only.
+ * zsk_preadv_device_indirect does not use this setting: on a zstd reader it
+ * is bounded by zsk_reader_zstd_census (below).
  */
 ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, unsigned seq_bytes);
 
 /*
  * zsk_preadv_device_async for a range list that is itself in DEVICE memory,
- * on a reader over a device image (zsk_reader_open_device, LZ4): the plan --
+ * on a reader over a device image (zsk_reader_open_device; LZ4, or zstd after
+ * zsk_reader_zstd_census, below): the plan --
  * which frames the ranges touch, their descriptors, the (range, frame)
  * segments -- is computed by kernels on @stream from the seek table the
  * reader keeps on the device, so ranges produced on the GPU (a sampler, an
@@ -436,8 +443,8 @@ ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, unsigned seq
  *
  * -1 + errbuf and nothing queued for: a NULL reader ("invalid reader"); a
  * reader not opened with zsk_reader_open_device ("device-planned read: needs
- * a device image"); a zstd reader ("device-planned read: zstd is not
- * supported"); a capturing stream ("device-planned read: stream is
+ * a device image"); a zstd reader whose census has not been taken
+ * ("device-planned read: zstd is not supported"); a capturing stream ("device-planned read: stream is
  * capturing"); nranges > 0 with NULL @d_ranges, NULL @d_result or max_frames
  * == 0; nranges > 0, buf_size > 0 and NULL @d_buf ("invalid buffer"); the
  * staging refusal above; a seek table that reaches past the image
@@ -452,6 +459,28 @@ ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, unsigned seq
  * reads on the same reader stay correct while such a call is in flight, and
  * zseek_reader_close waits for it.  Not for a capturing stream; not for host
  * images; a read of more than one batch is the caller's loop.
+ *
+ * A zstd reader.  The host never sees which frames a call touches, so it
+ * cannot size the zstd scratch from them; it sizes it from the file's census:
+ * accepted once zsk_reader_zstd_census has succeeded on the reader (before
+ * that: the refusal above), whatever zsk_reader_set_zstd_async says.  The
+ * batch is decoded by zsk_zstd_decode_frames_async's machinery with out_bytes
+ * = max_frames x the file's largest dSize, max_blocks = max_frames x the
+ * census' max_blocks and max_sequences = max_frames x its max_sequences, which
+ * no max_frames entries of the file exceed: no read of an unmodified image is
+ * ever refused for scratch, a file of many tiny blocks included.  -1,
+ * "device-planned read: max_frames frames exceed the zstd block bound" and
+ * nothing queued when max_frames x max_blocks reaches 2^29.  Growing the
+ * slot's zstd scratch to those bounds is one of the host waits.  Everything
+ * else is the contract above.
+ *
+ * The device still checks its own plan against the bounds: an image whose
+ * bytes were rewritten after the census (against zsk_reader_open_device's
+ * contract) so that a batch exceeds them is refused whole on the device, as in
+ * zsk_preadv_device_async -- every touched frame carries ZSK_ERR_SCRATCH, the
+ * ranges come out -1 or short, d_result[nranges] counts the rest, nothing
+ * outside the ranges' destinations is written, and the next call decodes
+ * normally.
  */
 #define ZSK_PLAN_OVERFLOW (-2)  /* more touched frames than the call reserved */
 #define ZSK_PLAN_SPAN     (-3)  /* the touched frames span 2 GiB or more of the image */
@@ -459,6 +488,45 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *reader,
     void *d_buf, size_t buf_size,
     const zsk_range_t *d_ranges, size_t nranges, size_t max_frames,
     int64_t *d_result, void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * The census of a zstd reader over a device image: one kernel, a lane per
+ * seek-table entry of the WHOLE file, walks every entry's frame, block and
+ * literals headers and sequence counts (the walk the decoder's planning kernel
+ * makes per batch) and keeps the maxima over the entries.  The image is
+ * immutable for the life of the reader, so the walk runs once: the first call
+ * takes the reader's exclusive lock, runs the kernel on the reader's own
+ * stream (its first batch slot's; the kernel reads only the image and the
+ * resident table), waits once for the three words to come back and stores
+ * them in the reader; every later call
+ * returns the stored numbers with no GPU work.  The reader keeps no device
+ * memory for it.
+ *
+ * What it is for: @max_frames x (max_blocks, max_sequences, max_dsize) bound
+ * any max_frames entries of the file, which is how zsk_preadv_device_indirect
+ * sizes its zstd scratch (above).  The same products are valid
+ * zsk_zstd_bounds_t for a caller of zsk_zstd_decode_frames_async over any
+ * max_frames entries of this file (out_bytes: wherever the caller's
+ * descriptors put them).  max_items is the largest single entry's item-slot
+ * need, for information: the scratch is sized from the other two.
+ * zsk_preadv_device_async does not use the census.
+ *
+ * 0 and *@census filled; a file with no frames gives all zeros.  -1 + errbuf
+ * for: a NULL reader ("invalid reader"); a NULL @census ("invalid census
+ * pointer"); a reader not opened with zsk_reader_open_device ("zstd census:
+ * needs a device image"); an LZ4 reader ("zstd census: not a zstd reader"); a
+ * seek table that reaches past the image ("unexpected EOF"); a HIP failure.
+ */
+typedef struct {
+    uint64_t frames;         /* seek-table entries walked                               */
+    uint64_t max_items;      /* most 8-byte item slots one entry's plan asks for        */
+    uint64_t max_blocks;     /* most zstd block headers in one entry                    */
+    uint64_t max_sequences;  /* most sequences one entry's sequence sections declare    */
+    uint32_t max_dsize;      /* the file's largest frame, decoded ...                   */
+    uint32_t max_csize;      /* ... and compressed                                      */
+} zsk_zstd_census_t;
+ZSEEK_EXPORT int zsk_reader_zstd_census(zseek_reader_t *reader, zsk_zstd_census_t *census,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 /*
  * The device-side building block, for callers of zsk_*_decode_frames: copy

@@ -1310,6 +1310,80 @@ extern "C" ZSEEK_EXPORT bool zsk_reader_set_zstd_async(zseek_reader_t *reader, u
     return true;
 }
 
+// The census of a zstd device image (zseek_hip.h): zstd_census_kernel over the
+// whole resident table, once; the maxima kept in the image's record.
+extern "C" ZSEEK_EXPORT int zsk_reader_zstd_census(zseek_reader_t *reader, zsk_zstd_census_t *census, char *errbuf)
+{
+    if (!reader) {
+        set_error(errbuf, "invalid reader");
+        return -1;
+    }
+    if (!census) {
+        set_error(errbuf, "invalid census pointer");
+        return -1;
+    }
+    DeviceImage *const img = reader->img;
+    if (!img) {
+        set_error(errbuf, "zstd census: needs a device image");
+        return -1;
+    }
+    if (reader->type != ZSEEK_ZSTD) {
+        set_error(errbuf, "zstd census: not a zstd reader");
+        return -1;
+    }
+    DeviceGuard keep_device;
+    std::unique_lock<std::shared_mutex> guard(reader->lock);
+    if (img->has_census.load(std::memory_order_acquire)) {
+        *census = img->census;
+        return 0;
+    }
+    const SeekTable &st = reader->st;
+    // (zsk_preadv_device_indirect's check: no entry reaches past the image)
+    if (st.c_off.back() > img->size) {
+        set_error(errbuf, "unexpected EOF");
+        return -1;
+    }
+    const size_t n = st.frames();
+    if (n >= 0x7FFFFFFFull) {   // (the decode's 31-bit frame count)
+        set_error(errbuf, "zstd census: too many frames");
+        return -1;
+    }
+    zsk_zstd_census_t c = {};
+    c.frames = n;
+    c.max_dsize = img->max_dsize;
+    c.max_csize = img->max_csize;
+    if (n) {
+        if (!ensure_lanes(reader, errbuf))
+            return -1;
+        DeviceCtx &g = *reader->lanes[0];
+        (void)hipSetDevice(g.device);
+        hipStream_t const q = g.slot[0].stream;
+        uint64_t *d_words = nullptr, words[kCensusWords] = {0};
+        hipError_t e = hipMalloc((void **)&d_words, sizeof(words));
+        if (e == hipSuccess && launch_zstd_census(img->d_coff, (uint32_t)n, img->ptr, d_words, q) != 0)
+            e = hipErrorLaunchFailure;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, q);
+        const hipError_t es = hipStreamSynchronize(q);   // (also before the words are freed)
+        if (e == hipSuccess)
+            e = es;
+        if (d_words)
+            (void)hipFree(d_words);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error(errbuf, "zstd census failed: %s", hipGetErrorString(e));
+            return -1;
+        }
+        c.max_items = words[0];
+        c.max_blocks = words[1];
+        c.max_sequences = words[2];
+    }
+    img->census = c;
+    img->has_census.store(true, std::memory_order_release);
+    *census = c;
+    return 0;
+}
+
 // Concurrent pread callbacks (zseek_hip.h): an opt-in beyond the reference's
 // contract, for callbacks that are safe to call from several threads.
 extern "C" ZSEEK_EXPORT bool zsk_reader_set_io_threads(zseek_reader_t *reader, int n)

@@ -32,6 +32,11 @@ struct DeviceImage {
     // the file's largest frame, decoded and compressed: what a device-planned
     // read (zsk_preadv_device_indirect) sizes its staging and its parse scratch by
     uint32_t max_dsize = 0, max_csize = 0;
+    // zsk_reader_zstd_census' result, stored under the reader's exclusive lock
+    // and published by has_census (read before the lock is taken): what a
+    // device-planned read of a zstd image sizes its zstd scratch by
+    zsk_zstd_census_t census = {};
+    std::atomic<bool> has_census{false};
 };
 
 struct zseek_reader {

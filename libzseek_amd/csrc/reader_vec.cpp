@@ -585,7 +585,10 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *r, vo
         set_error(errbuf, "device-planned read: needs a device image");
         return -1;
     }
-    if (r->type != ZSEEK_LZ4) {
+    // (zstd: the host cannot see the touched frames to size their scratch by;
+    // the file's census bounds any max_frames of them, zsk_reader_zstd_census)
+    const bool zstd = r->type == ZSEEK_ZSTD;
+    if (r->type != ZSEEK_LZ4 && !(zstd && img->has_census.load(std::memory_order_acquire))) {
         set_error(errbuf, "device-planned read: zstd is not supported");
         return -1;
     }
@@ -627,6 +630,16 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *r, vo
         set_error(errbuf, "device-planned read: max_frames frames exceed 4 GiB");
         return -1;
     }
+    // zstd: what any max_frames entries of the file need at most, by the census
+    // (zstd_caps.h); the decode's own limit on the block bound
+    ZstdBounds zb{0, 0, 0};
+    if (zstd)
+        zstd_census_bounds(max_frames, img->census.max_blocks, img->census.max_sequences, img->max_dsize,
+                           &zb.out_bytes, &zb.max_blocks, &zb.max_sequences);
+    if (nranges && zb.max_blocks >= (1ull << 29)) {
+        set_error(errbuf, "device-planned read: max_frames frames exceed the zstd block bound");
+        return -1;
+    }
     // (a table that puts frames past the image's end: image_span's refusal,
     // once for the whole table -- its prefix sums only grow)
     if (st.c_off.back() > img->size) {
@@ -653,8 +666,15 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *r, vo
     bool ok = c.reserve(0, L.total, err) && s.reserve(0, std::max<size_t>((size_t)max_frames * img->max_dsize, 16), 0, max_frames, false, err);
     // the parse scratch by the plan's scan layout: max_frames frames of at most
     // the file's largest compressed size, however far apart they lie
-    if (ok && !lz4_wave_batch(r->type, M) &&
-        split_scratch_reserve(&s.split, M, (uint64_t)M * slots_of(img->max_csize), q) != 0) {
+    // (zstd: the decode's scratch by the census bounds, grown here so that a
+    // failure is reported before anything is queued)
+    int scratch = 0;
+    if (ok && zstd)
+        scratch = zstd_scratch_reserve(&s.zs, M, zb.out_bytes, zstd_item_capacity(M, zb.max_blocks, zb.max_sequences),
+                                       zb.max_blocks, q);
+    else if (ok && !lz4_wave_batch(r->type, M))
+        scratch = split_scratch_reserve(&s.split, M, (uint64_t)M * slots_of(img->max_csize), q);
+    if (scratch != 0) {
         set_error(err, "allocate GPU decode buffers failed");
         ok = false;
     }
@@ -670,6 +690,8 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *r, vo
     // reserved above, each frame's size bounded by the file's largest
     DecodeBatch dec{r->type, q, reinterpret_cast<const FrameDesc *>(c.d + L.desc), M, img->base, img->max_dsize};
     dec.in_order = false;
+    if (zstd)
+        dec.zasync = &zb;   // (the device checks its plan against them: zstd_fit_kernel)
     dec.d_want = ck ? reinterpret_cast<const uint32_t *>(c.d + L.ck) : nullptr;
     ok = ok && decode_batch(s, dec) == hipSuccess;
     // (no host total: the gather's scan launch reads the segments' on the device)

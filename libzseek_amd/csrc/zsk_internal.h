@@ -357,6 +357,13 @@ int zstd_decode_frames_async(const FrameDesc *d_desc, uint32_t nframes, const ui
 // chunk boundaries into d_total; nothing comes back to the host
 int launch_zstd_plan_async(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_comp, ZstdScratch *s,
                            int32_t *d_status, uint64_t items_cap, const ZstdBounds &B, hipStream_t stream);
+// The census of a zstd file in device memory (zstd_plan.hip; zsk_reader_zstd_census):
+// the plan's walk over every one of its n entries, entry f the bytes
+// [d_coff[f], d_coff[f + 1]) of d_image, their largest item bound, block count
+// and sequence count into d_words[0..2] (device memory), queued on `stream`
+constexpr int kCensusWords = 3;
+int launch_zstd_census(const uint64_t *d_coff, uint32_t n, const uint8_t *d_image, uint64_t *d_words,
+                       hipStream_t stream);
 // The same for a request's few frames whose compressed bytes are also in host
 // memory (h_desc / h_comp: the reader's pinned upload, the same layout as
 // d_desc / d_comp): the plan -- zstd_plan_kernel's per-frame bounds

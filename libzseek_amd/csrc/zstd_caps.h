@@ -1,8 +1,9 @@
 // zstd_caps.h — the scratch capacities of the asynchronous zstd decode
 // (zsk_zstd_decode_frames_async): the host cannot wait for the plan's totals
 // there, so it sizes the scratch from bounds the caller states and the device
-// checks its own plan against them (zstd_fit_kernel, zstd_plan.hip).  No HIP
-// types: tests/native/zstd_caps_shim.cpp drives it.
+// checks its own plan against them (zstd_fit_kernel, zstd_plan.hip); and the
+// bounds a device-planned read takes from a file's census.  No HIP types:
+// tests/native/zstd_caps_shim.cpp and zstd_census_shim.cpp drive it.
 //
 // What the default bounds (zstd_bounds_default) cost in device memory: 2 items
 // of 8 bytes per sequence at out_bytes / 3 sequences, plus their padding, is
@@ -42,6 +43,26 @@ inline void zstd_bounds_default(uint32_t nframes, uint64_t out_bytes, uint64_t *
 {
     *max_sequences = out_bytes / 3;
     *max_blocks = 2ull * nframes + out_bytes / 16384;
+}
+
+// The bounds of a call that decodes any max_frames entries of one file, from
+// the file's census (zsk_reader_zstd_census: the most block headers and the
+// most declared sequences any one entry has, the largest decoded size): a
+// guarantee while the file's bytes stay what the census walked.  Every entry
+// has at most census_blocks blocks and census_sequences sequences, so
+// max_frames of them have at most the products, and zstd_item_capacity
+// (max_frames, products) covers the sum of their plan bounds; an entry of no
+// bytes (a padding descriptor) walks to a bound of 8 with no block and no
+// sequence, inside the 11 per entry.  A product past 64 bits saturates (no
+// device holds such a scratch: the caller refuses it).
+inline void zstd_census_bounds(uint64_t max_frames, uint64_t census_blocks, uint64_t census_sequences,
+                               uint32_t max_dsize, uint64_t *out_bytes, uint64_t *max_blocks,
+                               uint64_t *max_sequences)
+{
+    const auto times = [](uint64_t a, uint64_t b) { return a && b > ~0ull / a ? ~0ull : a * b; };
+    *out_bytes = times(max_frames, max_dsize);
+    *max_blocks = times(max_frames, census_blocks);
+    *max_sequences = times(max_frames, census_sequences);
 }
 
 }   // namespace zsk

@@ -1,8 +1,8 @@
 // zstd_plan.h — the per-entry plan of the zstd decoder: the 8-byte item slots
 // and block slots (tables, op list) a seek-table entry needs, from its frame,
 // block and literals section headers and sequence counts.  One walk for
-// zstd_plan_kernel (bytes through a buffer resource) and zstd_host_plan (bytes
-// from host memory).  No HIP types: tests/native/zstd_plan_shim.cpp drives it.
+// zstd_plan_kernel and zstd_census_kernel (bytes through a buffer resource)
+// and zstd_host_plan (bytes from host memory).  No HIP types: tests/native/zstd_plan_shim.cpp drives it.
 #pragma once
 
 #include <stdint.h>

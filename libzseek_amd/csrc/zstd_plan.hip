@@ -1,6 +1,7 @@
 // zstd_plan.hip -- the zstd decoder's plan: per entry the item and block slots
 // it needs (zstd_plan.h's walk), their scans into slot offsets, the block
-// offsets at the chunk boundaries; and the same on the host for a few frames.
+// offsets at the chunk boundaries; the same on the host for a few frames; and
+// the census of a whole file in device memory (the walk's maxima).
 #include <algorithm>
 
 #include "lz4_dev.h"
@@ -11,6 +12,19 @@ namespace zsk {
 namespace {
 
 using namespace lz4d;
+
+// zstd_plan.h's walk over the c_size bytes at p, through a buffer resource of
+// the entry's own: a byte at or past c_size reads as 0 and nothing outside the
+// entry is loaded
+__device__ __forceinline__ ZstdFramePlan entry_plan(const uint8_t *p, uint32_t c_size)
+{
+    const Span sp = make_span(p, c_size);
+    return zstd_frame_plan(
+        [&](uint32_t i) -> uint32_t {
+            return i < c_size ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(sp.r, sp.s0 + i, 0, 0) : 0u;
+        },
+        c_size);
+}
 
 // item bound per frame (lane per frame): 2 items per sequence + padding + 4 per
 // block; and the frame's block count (its table slots and op list)
@@ -34,14 +48,35 @@ __global__ __launch_bounds__(256) void zstd_plan_kernel(
         atomicMax(extent + 2, (unsigned long long)wd);
     if (f >= n)
         return;
-    const Span sp = make_span(comp + d.c_off, d.c_size);
-    const ZstdFramePlan P = zstd_frame_plan(
-        [&](uint32_t p) -> uint32_t {
-            return p < d.c_size ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(sp.r, sp.s0 + p, 0, 0) : 0u;
-        },
-        d.c_size);
+    const ZstdFramePlan P = entry_plan(comp + d.c_off, d.c_size);
     bound[f] = P.bound;
     bblk[f] = P.blocks;
+}
+
+// The census of a whole file in device memory (zsk_reader_zstd_census): a lane
+// per seek-table entry, entry f the image's bytes [c_off[f], c_off[f + 1]);
+// the largest item bound, block count and sequence count of any one entry,
+// a wave at a time, into words[0..2] (zeroed by the launcher).
+__global__ __launch_bounds__(256) void zstd_census_kernel(
+    const uint64_t *__restrict__ c_off, uint32_t n, const uint8_t *__restrict__ image,
+    unsigned long long *__restrict__ words)
+{
+    const uint32_t f = blockIdx.x * 256 + threadIdx.x;
+    ZstdFramePlan P = {0, 0, false, 0};
+    if (f < n) {
+        const uint64_t c0 = c_off[f];
+        P = entry_plan(image + c0, (uint32_t)(c_off[f + 1] - c0));
+    }
+    // (every lane of the wave is here again: a lane past n holds zeros)
+    const uint64_t wi = wave_max64(P.bound), wb = wave_max64(P.blocks), ws = wave_max64(P.sequences);
+    if ((threadIdx.x & 63) != 0)
+        return;
+    if (wi)
+        atomicMax(words, (unsigned long long)wi);
+    if (wb)
+        atomicMax(words + 1, (unsigned long long)wb);
+    if (ws)
+        atomicMax(words + 2, (unsigned long long)ws);
 }
 
 // exclusive scans of the per-frame item bounds and block counts ->
@@ -185,6 +220,20 @@ int launch_zstd_plan_async(const FrameDesc *d_desc, uint32_t nframes, const uint
     // (a grid of at least kChunks + 1 threads: the boundaries)
     hipLaunchKernelGGL(zstd_fit_kernel, dim3((nframes + 255) / 256), dim3(256), 0, stream, s->blk_base, nframes,
                        zstd_chunks(nframes), s->d_total, items_cap, B.max_blocks, B.out_bytes, d_status);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The census kernel over the n entries of the image whose table is d_coff
+// (n + 1 offsets), behind a memset of its three words.
+int launch_zstd_census(const uint64_t *d_coff, uint32_t n, const uint8_t *d_image, uint64_t *d_words,
+                       hipStream_t stream)
+{
+    if (hipMemsetAsync(d_words, 0, kCensusWords * sizeof(uint64_t), stream) != hipSuccess)
+        return -1;
+    if (n == 0)
+        return 0;
+    hipLaunchKernelGGL(zstd_census_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_coff, n, d_image,
+                       reinterpret_cast<unsigned long long *>(d_words));
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -81,6 +81,12 @@ class ZstdBoundsC(C.Structure):
     _fields_ = [("out_bytes", C.c_uint64), ("max_blocks", C.c_uint64), ("max_sequences", C.c_uint64)]
 
 
+class ZstdCensusC(C.Structure):
+    """zsk_zstd_census_t"""
+    _fields_ = [("frames", C.c_uint64), ("max_items", C.c_uint64), ("max_blocks", C.c_uint64),
+                ("max_sequences", C.c_uint64), ("max_dsize", C.c_uint32), ("max_csize", C.c_uint32)]
+
+
 class GpuStatsC(C.Structure):
     _fields_ = [("batches", C.c_uint64), ("frames_decoded", C.c_uint64),
                 ("bytes_decoded", C.c_uint64), ("bytes_uploaded", C.c_uint64),
@@ -129,6 +135,7 @@ EXPORTED = [
     "zsk_zstd_compress_scratch_size", "zsk_zstd_compress_frames", "zsk_zstd_image_bound", "zsk_zstd_build_image",
     "zsk_zstd_compress_scratch_size_ex", "zsk_zstd_compress_frames_ex",
     "zsk_zstd_bounds_default", "zsk_zstd_decode_frames_async", "zsk_reader_set_zstd_async",
+    "zsk_reader_zstd_census",
 ]
 
 _lib = None
@@ -177,6 +184,8 @@ def lib() -> C.CDLL:
                                                C.POINTER(ZstdBoundsC), C.c_void_p]
     L.zsk_reader_set_zstd_async.restype = C.c_bool
     L.zsk_reader_set_zstd_async.argtypes = [C.c_void_p, C.c_uint]
+    L.zsk_reader_zstd_census.restype = C.c_int
+    L.zsk_reader_zstd_census.argtypes = [C.c_void_p, C.POINTER(ZstdCensusC), C.c_char_p]
     L.zsk_lz4_decode_frames_ex.restype = C.c_int
     L.zsk_lz4_decode_frames_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_int]
@@ -678,6 +687,16 @@ class Reader:
         scratch sized at a sequence per seq_bytes decoded bytes (0: off; 1 and
         2: refused, False)."""
         return bool(lib().zsk_reader_set_zstd_async(self._h, seq_bytes))
+
+    def zstd_census(self) -> dict:
+        """zsk_reader_zstd_census (a zstd reader from open_device): the largest
+        item, block and sequence counts and sizes of any one seek-table entry,
+        walked once on the GPU; after it preadv_device_indirect accepts the
+        reader.  ZseekError when the call fails."""
+        c = ZstdCensusC()
+        if lib().zsk_reader_zstd_census(self._h, C.byref(c), self._err) != 0:
+            raise ZseekError(self.error)
+        return {k: getattr(c, k) for k, _ in ZstdCensusC._fields_}
 
     def close(self) -> None:
         if self._h:

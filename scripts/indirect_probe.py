@@ -22,7 +22,15 @@ the GPU time of one indirect call, its decode stages, and the GPU time of a
 call with max_frames 1 -- it overflows, so it runs the planning, result and
 fix kernels and decodes nothing: the planning kernels' share.
 
-    python scripts/indirect_probe.py [--size N] [--ranges N] [--count N] [--runs K] [--out FILE.json]
+`--codec zstd`: the same shape on a zstd image built in device memory by
+zsk_zstd_build_image.  The device-planned read needs the reader's census
+(zsk_reader_zstd_census: the host time of that call is reported -- it waits for
+its kernel -- taken after a small read has created the reader's lane); `today` is the host-planned zsk_preadv_device_async after
+zsk_reader_set_zstd_async(3).  Also reported: the reader's device memory after
+each variant's first call (each on a reader of its own), and the bounds the
+two size their zstd scratch by -- the census' against the policy's.
+
+    python scripts/indirect_probe.py [--codec lz4|zstd] [--size N] [--ranges N] [--count N] [--runs K] [--out FILE.json]
 """
 from __future__ import annotations
 
@@ -56,6 +64,7 @@ def main() -> None:
     ap.add_argument("--count", type=int, default=4096)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--codec", choices=["lz4", "zstd"], default="lz4")
     args = ap.parse_args()
 
     import torch
@@ -64,15 +73,45 @@ def main() -> None:
     L = zs.lib()
     N, cnt = args.ranges, args.count
     data = zs.synth_buffer(args.size)
-    img = zs.lz4_seekable(data, FRAME)
+    zstd = args.codec == "zstd"
     d_data = torch.from_numpy(data).to("cuda")
-    d_img = torch.from_numpy(img).to("cuda")
+    if zstd:
+        d_img = zs.zstd_build_image(d_data, FRAME)
+        img = d_img
+    else:
+        img = zs.lz4_seekable(data, FRAME)
+        d_img = torch.from_numpy(img).to("cuda")
     err = C.create_string_buffer(zs.ERRBUF)
-    h = L.zsk_reader_open_device(d_img.data_ptr(), d_img.numel(), 0, err)
-    if not h:
-        sys.exit("open_device: " + err.value.decode())
     loose = 2 * N                                            # a range of <= 64 KiB touches at most two frames
-    L.zsk_reader_set_batch_bytes(h, loose * FRAME)           # one batch for every variant
+
+    def open_reader():
+        hh = L.zsk_reader_open_device(d_img.data_ptr(), d_img.numel(), 0, err)
+        if not hh:
+            sys.exit("open_device: " + err.value.decode())
+        L.zsk_reader_set_batch_bytes(hh, loose * FRAME)      # one batch for every variant
+        if zstd and not L.zsk_reader_set_zstd_async(hh, 3):
+            sys.exit("set_zstd_async failed")
+        return hh
+
+    def device_memory(hh):
+        g = zs.GpuStatsC()
+        L.zsk_reader_gpu_stats_ex(hh, C.byref(g), C.sizeof(g))
+        return int(g.device_memory)
+
+    h = open_reader()
+    census = None
+    if zstd:
+        c = zs.ZstdCensusC()
+        # (a small read first: the reader's lane -- streams, events -- exists before the census is timed)
+        warm = torch.empty(4096, dtype=torch.uint8, device="cuda")
+        if L.zsk_pread_device(h, warm.data_ptr(), 4096, 0, None, err) != 4096:
+            sys.exit("pread_device: " + err.value.decode())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if L.zsk_reader_zstd_census(h, C.byref(c), err) != 0:
+            sys.exit("zstd census: " + err.value.decode())
+        census = {k: int(getattr(c, k)) for k, _ in zs.ZstdCensusC._fields_}
+        census["call_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
     S = torch.cuda.Stream()
     rng = np.random.default_rng(1)
     offs = np.sort(rng.integers(0, args.size - cnt, N)).astype(np.int64)
@@ -103,6 +142,31 @@ def main() -> None:
                                             d_res.data_ptr(), S.cuda_stream, err)
 
     variants = {"today": today, "indirect": lambda: indirect(loose), "indirect_tight": lambda: indirect(tight)}
+    memory = None
+    if zstd:
+        # each variant's first call on a reader of its own: what it makes the reader hold
+        memory = {}
+        keep = h
+        for name, fn in variants.items():
+            h = open_reader()
+            if L.zsk_reader_zstd_census(h, C.byref(zs.ZstdCensusC()), err) != 0:
+                sys.exit("zstd census: " + err.value.decode())
+            base = device_memory(h)
+            with torch.cuda.stream(S):
+                ret = fn()
+                S.synchronize()
+            if ret != 0:
+                sys.exit(f"{name}: {ret} {err.value.decode()}")
+            memory[name] = {"before": base, "after": device_memory(h)}
+            L.zseek_reader_close(h, None, None)
+        h = keep
+        blocks, seqs = census["max_blocks"], census["max_sequences"]
+        memory["bounds"] = {
+            "census": {mf: {"out_bytes": mf * FRAME, "max_blocks": mf * blocks, "max_sequences": mf * seqs}
+                       for mf in (loose, tight)},
+            # zsk_reader_set_zstd_async(3) for the frames the list touches
+            "policy_touched": {"out_bytes": touched * FRAME, "max_blocks": touched * (2 + FRAME // 16384),
+                               "max_sequences": touched * FRAME // 3}}
     times = {k: [] for k in variants}
     with torch.cuda.stream(S):
         for rep in range(args.runs + 1):
@@ -118,23 +182,29 @@ def main() -> None:
                     raise RuntimeError(f"{name}: wrong bytes or results ({ret}) {err.value.decode()}")
                 if rep:
                     times[name].append(t * 1e3)
-    result = {"input_bytes": args.size, "image_bytes": int(img.size), "ranges": N, "count": cnt, "runs": args.runs,
+    result = {"codec": args.codec, "input_bytes": args.size, "image_bytes": int(d_img.numel()), "ranges": N, "count": cnt, "runs": args.runs,
               "touched_frames": touched, "max_frames": {"indirect": loose, "indirect_tight": tight},
               "device": torch.cuda.get_device_name(0),
               "call_ms": {k: row(v, "ms") for k, v in times.items()}}
+    if zstd:
+        result["census"], result["device_memory"] = census, memory
+        print(json.dumps({"census": census, "device_memory": memory}), flush=True)
     print(json.dumps({"call_ms": result["call_ms"], "touched_frames": touched}), flush=True)
 
     # GPU time by HIP events: a whole call, and a call that only plans (max_frames 1 overflows)
-    gpu = {"indirect": [], "indirect_tight": [], "plan_only": []}
+    timed = [("indirect", loose), ("indirect_tight", tight), ("plan_only", 1)]
+    if zstd:
+        timed.append(("today", 0))                           # the host-planned call's stages, to compare
+    gpu = {name: [] for name, _ in timed}
     stages = {}
     with torch.cuda.stream(S):
-        for name, mf in (("indirect", loose), ("indirect_tight", tight), ("plan_only", 1)):
+        for name, mf in timed:
             L.zsk_kernel_timing(1)
             for rep in range(args.runs + 1):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 S.synchronize()
                 e0.record(S)
-                ret = indirect(mf)
+                ret = today() if name == "today" else indirect(mf)
                 e1.record(S)
                 S.synchronize()
                 if ret != 0 or int(d_res[N]) != (zs.PLAN_OVERFLOW if name == "plan_only" else N):
@@ -144,6 +214,8 @@ def main() -> None:
             ms = (C.c_double * 8)()
             n = L.zsk_kernel_times(ms, 8)
             stages[name] = {"launches": n, "plan_parse_execute_handoff_ms": [round(ms[i], 4) for i in range(4)]}
+            if zstd:   # (its spans: frame, sequence, Huffman and execute kernels, summed over the chunks)
+                stages[name]["zstd_frame_seq_huf_exec_ms"] = [round(ms[i], 4) for i in range(4, 8)]
             L.zsk_kernel_timing(0)
     result["gpu_ms"] = {k: row(v, "ms") for k, v in gpu.items()}
     result["decode_stages"] = stages
