@@ -9,7 +9,8 @@
 //
 //   * one sub-step parses one whole sequence — token, literal length with at
 //     most one extension byte, offset, match length with at most one
-//     extension byte — from two 4-byte reads of a 512-byte per-lane LDS ring,
+//     extension byte — from two 4-byte reads of a per-lane LDS ring (R bytes,
+//     lean_ring.h: the chain carries the ring position of its read pointer),
 //     checks every liblz4 rule that applies to it, and stores its item(s)
 //     with one 16-byte store (a short item's second half is overwritten by
 //     the next item);
@@ -29,6 +30,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "lean_ring.h"
 #include "lz4_dev.h"
 #include "zsk_internal.h"
 
@@ -41,27 +43,53 @@ using namespace lz4d;
 constexpr uint32_t kItemExt = 0x80000000u;
 constexpr uint32_t kItemPos = 0x3FFFFFFFu;
 constexpr uint32_t kLW = 4;              // waves per workgroup
-constexpr uint32_t kRing = 256;          // per-lane ring bytes
-// per lane: ring [0, 256), mirror of ring bytes [0, 16) at [256, 272) (4-byte
-// reads never wrap), a 32-byte sink for disabled writes at [272, 304), the
-// item buffer (32 slots = two 128-byte lines) at [304, 560)
-constexpr uint32_t kMirror = 256, kSink = 272, kIBuf = 304;
-constexpr uint32_t kStride = 560;        // bytes between lanes' areas
-// (an odd dword count spreads same-offset accesses over every LDS bank but
-// misaligns the 16-byte ring and item writes: 564 / 568 bytes 4.46 / 4.32 vs
-// 4.02 ms per launch at config 2)
+// A lane's LDS area: the ring [0, R) (R a multiple of 32, any such length),
+// the mirror of ring bytes [0, 16) at [R, R + 16) (4-byte reads never wrap),
+// a 32-byte sink for disabled writes behind it -- or, WSINK, none: the wave's
+// lanes share one 32-byte sink outside the areas, which is what lets R = 320
+// fit a CU's LDS -- and the item buffer (32 slots = two 128-byte lines).
+// R = 256: ring [0, 256), mirror [256, 272), sink [272, 304), items
+// [304, 560).  SLOT: bytes a fill slot loads (64, 96 or 128: 32-byte pieces).
+// CARRY: ring positions are carried and wrapped (lean_ring.h); else, R a
+// power of two, every ring address is its coordinate masked, as it was
+// before R became a constant -- a "position" is then the coordinate itself.
+// The single-wave kernel keeps that form: with the fill, the flush and the
+// chain on one instruction stream the carried positions cost it 2 % (block
+// parse at 1 MiB frames 0.980 -> 1.000 ms), where the pair kernel's parser
+// gains by them (section 3 of DESIGN).
+template <uint32_t R_, uint32_t SLOT_, bool WSINK_, bool CARRY_ = true>
+struct Cfg {
+    using Ring = LeanRing<R_>;
+    static constexpr uint32_t R = R_, kPieces = SLOT_ / 32;
+    static constexpr bool kWaveSink = WSINK_, kCarry = CARRY_;
+    static_assert(CARRY_ || Ring::kPow2, "masked coordinates need a power of two");
+    static constexpr uint32_t kMirror = Ring::kMirror, kSink = R_ + 16, kIBuf = kSink + (WSINK_ ? 0 : 32);
+    static constexpr uint32_t kStride = kIBuf + 256;   // bytes between lanes' areas
+    // (an odd dword count spreads same-offset accesses over every LDS bank but
+    // misaligns the 16-byte ring and item writes: 564 / 568 bytes 4.46 / 4.32 vs
+    // 4.02 ms per launch at config 2 and R = 256)
+    static_assert(SLOT_ % 32 == 0 && kPieces >= 1 && kPieces <= 4 && kStride % 16 == 0, "lane area");
+};
+using BlockCfg = Cfg<256, 64, false, false>;   // the block route's single-wave kernel
+// The frame route's pair kernel: 96-byte slots (48 bytes per mover sub-step
+// against the ~40 a config-2 parser consumes; 64-byte slots left it short:
+// plan + parse 0.930 -> 0.898 ms).  The ring stays 256 bytes: 288 and 320
+// measured the same at either slot width (tuning variants).
+using PairCfg = Cfg<256, 96, false>;
 constexpr uint32_t kFlush = 8;           // item lines written per flush (one store)
-// The fill keeps the ring within [ip, ip + kRing - 16) and moves in 32-byte
-// slots; a literal run whose offset lies past what has arrived is taken in
+// The fill keeps the ring within [ip, ip + R - 16) and moves in 32-byte
+// pieces; a literal run whose offset lies past what has arrived is taken in
 // two halves (fast())
 constexpr uint32_t kOff = 0x80000000u;   // out-of-range buffer offset: op disabled
 
 enum : uint32_t { P_TOKEN = 0, P_LEXT, P_OFF, P_MEXT, P_BHDR, P_END, P_DONE };
 
+template <uint32_t P>
 struct Fill {
-    u32x4 a, b, c, d;   // ring bytes [x, x + 64): the first 32, and the second 32 if h2
-    uint32_t x;         // ring coordinate, or kOff
-    bool h2;
+    u32x4 v[2 * P];     // stream bytes [x, x + 32 * n), 16 per register quad
+    uint32_t x;         // coordinate of the first byte, or kOff
+    uint32_t rx;        // its ring position
+    uint32_t n;         // 32-byte pieces loaded (0: none)
 };
 
 struct Lane {
@@ -69,7 +97,10 @@ struct Lane {
     uint32_t cx0;                      // coordinate of frame byte 0 in cin
     uint32_t clen, dlen;
     uint32_t ring;                     // LDS address of the lane's ring
+    uint32_t sink;                     // LDS address of 32 bytes that take disabled writes
     uint32_t fill, avail;              // next coordinate to load; coordinates < avail are in the ring
+    uint32_t rfill;                    // ring position of fill (the fill's side)
+    uint32_t rip;                      // ring position of cx0 + ip, below R + 3 (the parse chain's side)
     uint32_t ph;
     int32_t st;
     uint32_t ip, op, fail_op;
@@ -117,9 +148,11 @@ __device__ __forceinline__ void lds_w128(uint32_t a, u32x4 v)
         (__attribute__((address_space(3))) void *)(uintptr_t)a) = v;
 }
 
+// (by coordinate, with a division: the exact step and the frame header)
+template <class C>
 __device__ __forceinline__ uint32_t raddr(const Lane &L, uint32_t x)
 {
-    return L.ring + (x & (kRing - 1));
+    return L.ring + C::Ring::of(x);
 }
 
 __device__ __forceinline__ bool have(const Lane &L, uint32_t p, uint32_t n)
@@ -127,32 +160,45 @@ __device__ __forceinline__ bool have(const Lane &L, uint32_t p, uint32_t n)
     return L.cx0 + p + n <= L.avail;
 }
 
+template <class C>
 __device__ __forceinline__ uint32_t rb(const Lane &L, uint32_t p)
 {
-    return lds_u8(raddr(L, L.cx0 + p));
+    return lds_u8(raddr<C>(L, L.cx0 + p));
 }
 
-// 4 frame bytes from p: two adjacent dwords (the mirror covers the wrap)
-__device__ __forceinline__ uint32_t r4(const Lane &L, uint32_t p)
+// 4 stream bytes from ring position pos (< R + 12): two adjacent dwords (the
+// mirror covers the wrap)
+template <class C>
+__device__ __forceinline__ uint32_t r4(const Lane &L, uint32_t pos)
 {
-    const uint32_t x = L.cx0 + p;
-    const uint32_t a = L.ring + (x & (kRing - 4));
-    return __builtin_amdgcn_alignbyte(lds_u32(a + 4), lds_u32(a), x & 3);
+    const uint32_t a = L.ring + (C::kCarry ? C::Ring::read4_at(pos) : pos & (C::R - 4));
+    return __builtin_amdgcn_alignbyte(lds_u32(a + 4), lds_u32(a), pos & 3);
 }
 
-// ring bytes [x, x + 32) (x 32-aligned) from a retired slot, or into the
-// sink when off; ring bytes [0, 16) are mirrored at kMirror
-__device__ __forceinline__ void ring_put(const Lane &L, uint32_t x, u32x4 a, u32x4 b, bool on)
+// a 32-byte piece of a retired slot to ring position pos (32-aligned), or
+// into the sink when off; ring bytes [0, 16) are mirrored at kMirror
+template <class C>
+__device__ __forceinline__ void ring_put(const Lane &L, uint32_t pos, u32x4 a, u32x4 b, bool on)
 {
-    const uint32_t i = x & (kRing - 1);
-    lds_w128(L.ring + (on ? i : kSink), a);
-    lds_w128(L.ring + (on ? i + 16 : kSink + 16), b);
-    lds_w128(L.ring + ((on && i == 0) ? kMirror : kSink), a);
+    const uint32_t i = C::kCarry ? pos : pos & (C::R - 1);
+    const uint32_t at = L.ring + i;
+    lds_w128(on ? at : L.sink, a);
+    lds_w128(on ? at + 16 : L.sink + 16, b);
+    lds_w128((on && C::Ring::piece_mirrored(i)) ? L.ring + C::kMirror : L.sink, a);
 }
 
+template <class C>
 __device__ __forceinline__ uint32_t rd32(const Lane &L, uint32_t p)
 {
-    return rb(L, p) | (rb(L, p + 1) << 8) | (rb(L, p + 2) << 16) | (rb(L, p + 3) << 24);
+    return rb<C>(L, p) | (rb<C>(L, p + 1) << 8) | (rb<C>(L, p + 2) << 16) | (rb<C>(L, p + 3) << 24);
+}
+
+// the chain's ring position after the exact step or the set-up moved ip
+template <class C>
+__device__ __forceinline__ void rip_sync(Lane &L)
+{
+    if (C::kCarry)
+        L.rip = C::Ring::of(L.cx0 + L.ip);
 }
 
 __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t x)
@@ -195,17 +241,18 @@ __device__ __forceinline__ bool emit(Lane &L, uint32_t lsrc, uint32_t lit, uint3
 }
 
 // ---- frame header (LZ4F_decodeHeader order; as parse_frame) ------------------
+template <class C>
 __device__ __forceinline__ int32_t hdr_status(Lane &L)
 {
     const uint32_t clen = L.clen;
     if (clen < 7)
         return ST_HDR_INCOMPLETE;
-    const uint32_t magic = rd32(L, 0);
+    const uint32_t magic = rd32<C>(L, 0);
     if ((magic & 0xFFFFFFF0u) == 0x184D2A50u)
         return ST_SHORT_FRAME;
     if (magic != kLz4Magic)
         return ST_FRAME_TYPE;
-    const uint32_t flg = rb(L, 4), bd = rb(L, 5);
+    const uint32_t flg = rb<C>(L, 4), bd = rb<C>(L, 5);
     if (flg & 0x14)   // block / content checksums: the wave kernel verifies them
         return ST_NOT_RUN;
     const uint32_t dictid = flg & 1;
@@ -228,11 +275,11 @@ __device__ __forceinline__ int32_t hdr_status(Lane &L)
     uint32_t acc = 0x165667B1u + n;
     uint32_t i = 0;
     for (; i + 4 <= n; i += 4) {
-        acc += rd32(L, 4 + i) * 0xC2B2AE3Du;
+        acc += rd32<C>(L, 4 + i) * 0xC2B2AE3Du;
         acc = ((acc << 17) | (acc >> 15)) * 0x27D4EB2Fu;
     }
     for (; i < n; i++) {
-        acc += rb(L, 4 + i) * 0x165667B1u;
+        acc += rb<C>(L, 4 + i) * 0x165667B1u;
         acc = ((acc << 11) | (acc >> 21)) * 0x9E3779B1u;
     }
     acc ^= acc >> 15;
@@ -240,15 +287,16 @@ __device__ __forceinline__ int32_t hdr_status(Lane &L)
     acc ^= acc >> 13;
     acc *= 0xC2B2AE3Du;
     acc ^= acc >> 16;
-    if (((acc >> 8) & 0xFF) != rb(L, hdr - 1))
+    if (((acc >> 8) & 0xFF) != rb<C>(L, hdr - 1))
         return ST_HDR_CHECKSUM;
     L.indep = (flg >> 5) & 1;
     L.csz_flag = csz;
     L.bsid = bsid;
     if (csz)
-        L.csize = (uint64_t)rd32(L, 6) | ((uint64_t)rd32(L, 10) << 32);
+        L.csize = (uint64_t)rd32<C>(L, 6) | ((uint64_t)rd32<C>(L, 10) << 32);
     L.max_block = 1u << (8 + 2 * bsid);
     L.ip = hdr;
+    rip_sync<C>(L);
     return -1;
 }
 
@@ -272,20 +320,25 @@ __device__ __forceinline__ int32_t hdr_status(Lane &L)
 // (fe: the flush-table entry read with the token; the line it names is read
 // with the offset, so the flush adds no LDS round trip of its own; FV false,
 // the pair kernel's parser wave: no flush read, the mover wave does it)
-template <bool FV = true>
+// Ring addressing: rip is the position of ip; the position of q is one add
+// and one conditional subtract from it (LeanRing::adv), the next ip's lies 2
+// or 3 past q's or ip's and is left unwrapped -- the mirror serves it.
+template <class C, bool FV = true>
 __device__ __forceinline__ bool fast(Lane &L, uint32_t fe, uint32_t pc, u32x4 &fv)
 {
-    const uint32_t ip = L.ip, ph = L.ph;
+    using Ring = typename C::Ring;
+    const uint32_t ip = L.ip, ph = L.ph, rip = C::kCarry ? L.rip : L.cx0 + ip;
     const bool po = ph == P_OFF;
-    const uint32_t w = r4(L, ip);
+    const uint32_t w = r4<C>(L, rip);
     const uint32_t tok = w & 0xFF, e = (w >> 8) & 0xFF;
     const bool lext = (tok >> 4) == 15;
     const uint32_t lit = lext ? 15 + e : tok >> 4;
     const uint32_t p = ip + (lext ? 2 : 1);
     const uint32_t q = p + lit;
+    const uint32_t rq = C::kCarry ? Ring::adv(rip, (lext ? 2 : 1) + lit) : L.cx0 + q;
     if (FV)
         fv = *lp<u32x4>(fe + 16 * pc);
-    const uint32_t o4q = r4(L, q);
+    const uint32_t o4q = r4<C>(L, rq);
     const uint32_t qq = po ? ip : q;
     const uint32_t o4 = po ? w : o4q;
     const uint32_t mtok = po ? L.tok : tok;
@@ -293,6 +346,8 @@ __device__ __forceinline__ bool fast(Lane &L, uint32_t fe, uint32_t pc, u32x4 &f
     const bool mext = (mtok & 15) == 15;
     const uint32_t ml = (mext ? 15 + e2 : mtok & 15) + kMinMatch;
     const uint32_t nip = qq + (mext ? 3 : 2);
+    // (in P_OFF rip is wrapped: the literal half or the exact step left it)
+    const uint32_t rnip = Ring::adv_lazy(po ? rip : rq, mext ? 3 : 2);
     const uint32_t lt = po ? L.nlit : lit, ls = po ? L.lsrc : p;
     const uint32_t cop = po ? L.op : L.op + lit;
     const int32_t s_av = (int32_t)(L.avail - (L.cx0 + qq + 3));
@@ -321,6 +376,8 @@ __device__ __forceinline__ bool fast(Lane &L, uint32_t fe, uint32_t pc, u32x4 &f
     L.ib2 = ml;
     L.nk = go ? (big ? 2 : 1) : 0;
     L.ip = go ? nip : (half ? q : ip);
+    if (C::kCarry)
+        L.rip = go ? rnip : (half ? rq : rip);
     L.op = go ? cop + ml : (half ? cop : L.op);
     L.lsrc = half ? p : L.lsrc;
     L.nlit = half ? lit : L.nlit;
@@ -401,6 +458,7 @@ __device__ __forceinline__ void match_done(Lane &L, uint32_t p, uint32_t off, ui
     L.ph = P_TOKEN;
 }
 
+template <class C>
 __device__ __forceinline__ void slow(Lane &L)
 {
     if (L.k + 2 > L.kf + 32)
@@ -413,7 +471,7 @@ __device__ __forceinline__ void slow(Lane &L)
         }
         if (!have(L, p, 1))
             return;
-        const uint32_t tok = rb(L, p++);
+        const uint32_t tok = rb<C>(L, p++);
         L.tok = tok;
         if ((tok >> 4) != 15) {
             lit_done(L, p, tok >> 4);
@@ -439,7 +497,7 @@ __device__ __forceinline__ void slow(Lane &L)
                 L.acc = lit;
                 return;
             }
-            e = rb(L, p++);
+            e = rb<C>(L, p++);
             lit += e;
         } while (e == 255);
         lit_done(L, p, lit);
@@ -449,7 +507,7 @@ __device__ __forceinline__ void slow(Lane &L)
         uint32_t p = L.ip;
         if (!have(L, p, 2))
             return;
-        const uint32_t off = rb(L, p) | (rb(L, p + 1) << 8);
+        const uint32_t off = rb<C>(L, p) | (rb<C>(L, p + 1) << 8);
         p += 2;
         if ((L.tok & 15) != 15) {
             match_done(L, p, off, L.tok & 15);
@@ -472,7 +530,7 @@ __device__ __forceinline__ void slow(Lane &L)
                 L.acc = ml;
                 return;
             }
-            e = rb(L, p++);
+            e = rb<C>(L, p++);
             ml += e;
             if (p >= L.iend - (kLastLiterals - 1)) {
                 fail_block(L);
@@ -494,7 +552,7 @@ __device__ __forceinline__ void slow(Lane &L)
         }
         if (!have(L, L.ip, 4))
             return;
-        const uint32_t bh = rd32(L, L.ip);
+        const uint32_t bh = rd32<C>(L, L.ip);
         L.ip += 4;
         if (bh == 0) {
             L.ph = P_END;
@@ -552,24 +610,26 @@ __device__ __forceinline__ void slow(Lane &L)
 // and HBM offset into the wave's table and count it flushed; next sub-step
 // the table entry is read with the token, the line with the offset, and
 // 8-lane group g stores line g — one 16-byte piece per lane, whole lines.
+template <class C>
 __device__ __forceinline__ uint32_t flush_hand(Lane &L, uint32_t tab)
 {
     const bool ready = L.k - L.kf >= 16;
     const uint64_t rm = __ballot(ready);
     const uint32_t j = __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u));
     const bool mine = ready && j < kFlush;
-    const uint32_t line = L.ring + kIBuf + 128 * ((L.kf >> 4) & 1);
+    const uint32_t line = L.ring + C::kIBuf + 128 * ((L.kf >> 4) & 1);
     *lp<uint64_t>(mine ? tab + 8 * j : tab + 8 * kFlush) = ((uint64_t)(8 * (L.ib + L.kf)) << 32) | line;
     L.kf = mine ? L.kf + 16 : L.kf;
     return min((uint32_t)__builtin_popcountll(rm), kFlush);
 }
 
 // the sub-step's staged item(s) into the lane's buffer (slots k, k + 1 mod 32)
+template <class C>
 __device__ __forceinline__ void put_items(Lane &L)
 {
-    const uint32_t ibuf = L.ring + kIBuf;
-    const uint32_t a0 = L.nk ? ibuf + 8 * (L.k & 31) : L.ring + kSink;
-    const uint32_t a1 = L.nk == 2 ? ibuf + 8 * ((L.k + 1) & 31) : L.ring + kSink + 8;
+    const uint32_t ibuf = L.ring + C::kIBuf;
+    const uint32_t a0 = L.nk ? ibuf + 8 * (L.k & 31) : L.sink;
+    const uint32_t a1 = L.nk == 2 ? ibuf + 8 * ((L.k + 1) & 31) : L.sink + 8;
     *lp<uint64_t>(a0) = ((uint64_t)L.ibw << 32) | L.ia;
     *lp<uint64_t>(a1) = ((uint64_t)L.ib2 << 32) | L.ia2;
     L.k += L.nk;
@@ -577,33 +637,46 @@ __device__ __forceinline__ void put_items(Lane &L)
 }
 
 // retire slot S into the ring when it holds the stream's next bytes
-__device__ __forceinline__ void fill_retire(Lane &L, const Fill &S)
+template <class C>
+__device__ __forceinline__ void fill_retire(Lane &L, const Fill<C::kPieces> &S)
 {
     const bool in = S.x == L.avail;
-    ring_put(L, S.x, S.a, S.b, in);
-    ring_put(L, S.x + 32, S.c, S.d, in && S.h2);
-    L.avail = in ? L.avail + (S.h2 ? 64 : 32) : L.avail;
+#pragma unroll
+    for (uint32_t i = 0; i < C::kPieces; i++)
+        ring_put<C>(L, C::kCarry ? C::Ring::piece_at(S.rx, i) : S.x + 32 * i, S.v[2 * i], S.v[2 * i + 1],
+                    in && i < S.n);
+    L.avail = in ? L.avail + 32 * S.n : L.avail;
 }
 
 // restart the stream at need_x if that byte was never requested (a long
-// literal run was skipped), then issue S's next loads: 32 bytes if that
-// leaves every byte from need_x on intact, and 32 more if those do too
-__device__ __forceinline__ void fill_issue(Lane &L, Fill &S, uint32_t need_x, bool live)
+// literal run was skipped: the ring position restarts with a division), then
+// issue S's next loads: 32 bytes if that leaves every byte from need_x on
+// intact, and 32 more while those do too, up to the slot's width
+template <class C>
+__device__ __forceinline__ void fill_issue(Lane &L, Fill<C::kPieces> &S, uint32_t need_x, bool live)
 {
     const bool jump = need_x >= L.fill;
     L.fill = jump ? need_x & ~31u : L.fill;
+    if (C::kCarry)
+        L.rfill = jump ? C::Ring::of(L.fill) : L.rfill;
     L.avail = jump ? L.fill : L.avail;
-    const uint32_t lim = need_x + kRing - 16;
-    const bool fl = live & (L.fill < L.cx0 + L.clen) & (L.fill + 32 <= lim);
-    const bool f2 = fl & (L.fill + 32 < L.cx0 + L.clen) & (L.fill + 64 <= lim);
-    const uint32_t fx = fl ? L.fill : kOff;
-    S.x = fx;
-    S.h2 = f2;
-    S.a = bload16(L.cin, fx);
-    S.b = bload16(L.cin, fl ? fx + 16 : kOff);
-    S.c = bload16(L.cin, f2 ? fx + 32 : kOff);
-    S.d = bload16(L.cin, f2 ? fx + 48 : kOff);
-    L.fill = fl ? L.fill + (f2 ? 64 : 32) : L.fill;
+    const uint32_t lim = need_x + C::R - 16, end = L.cx0 + L.clen;
+    bool on = live;
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < C::kPieces; i++) {
+        on = on & (L.fill + 32 * i < end) & (L.fill + 32 * (i + 1) <= lim);
+        const uint32_t fx = on ? L.fill + 32 * i : kOff;
+        S.v[2 * i] = bload16(L.cin, fx);
+        S.v[2 * i + 1] = bload16(L.cin, on ? fx + 16 : kOff);
+        n += on;
+    }
+    S.x = n ? L.fill : kOff;
+    S.rx = C::kCarry ? L.rfill : 0;
+    S.n = n;
+    L.fill += 32 * n;
+    if (C::kCarry)
+        L.rfill = C::Ring::adv(L.rfill, 32 * n);
 }
 
 template <int DIAG>
@@ -620,15 +693,15 @@ __device__ __forceinline__ void flush_store(const Lane &L, uint64_t fe, const u3
 // sequence (fast, else the exact step where needed), buffer its item(s),
 // store the lines handed over last sub-step and hand over new ones, issue
 // S's next load.  Branch-free but for the exact step.
-template <bool SLOW, bool FILL, int DIAG>
-__device__ __forceinline__ void sub(Lane &L, Fill &S, uint32_t lane, uint32_t tab, uint32_t &fcnt)
+template <class C, bool SLOW, bool FILL, int DIAG>
+__device__ __forceinline__ void sub(Lane &L, Fill<C::kPieces> &S, uint32_t lane, uint32_t tab, uint32_t &fcnt)
 {
     if (FILL)
-        fill_retire(L, S);
+        fill_retire<C>(L, S);
     const uint32_t g = lane >> 3, pc = lane & 7;
     const uint64_t fe = *lp<uint64_t>(tab + 8 * (g < fcnt ? g : kFlush));
     u32x4 fv;
-    const bool need = fast(L, (uint32_t)fe, pc, fv);
+    const bool need = fast<C>(L, (uint32_t)fe, pc, fv);
     if (DIAG & 4) {
         L.cnt[0] += L.nk != 0;
         L.cnt[1] += need;
@@ -644,25 +717,27 @@ __device__ __forceinline__ void sub(Lane &L, Fill &S, uint32_t lane, uint32_t ta
     if (SLOW && __builtin_expect(__ballot(need) != 0, 0)) {
         if (DIAG & 4)
             L.cnt[4] += 1;
-        if (need)
-            slow(L);
+        if (need) {
+            slow<C>(L);
+            rip_sync<C>(L);
+        }
     }
     // after the handed-over line was read
-    put_items(L);
+    put_items<C>(L);
     if (!(DIAG & 32)) {
         // a second sequence in the same sub-step when its bytes are in the
         // ring: the fill, flush and loop work then serve two (config 2, plan +
         // parse: 1.085 -> 1.032 ms; DIAG 32, tuning: one sequence, as round 3)
         u32x4 dv;
-        (void)fast(L, L.ring + kSink, 0, dv);
-        put_items(L);
+        (void)fast<C>(L, L.sink, 0, dv);
+        put_items<C>(L);
     }
     wave_lds_sync();
-    fcnt = flush_hand(L, tab);
+    fcnt = flush_hand<C>(L, tab);
     wave_lds_sync();
     if (!FILL)
         return;
-    fill_issue(L, S, L.cx0 + L.ip, L.ph < P_END);
+    fill_issue<C>(L, S, L.cx0 + L.ip, L.ph < P_END);
 }
 
 // The wave's frames [clo, chi) and item slots [ilo, ihi) as two buffer
@@ -687,6 +762,7 @@ __device__ __forceinline__ bool lane_setup(Lane &L, const FrameDesc &d, bool act
     L.dlen = d.d_size;
     L.fill = L.cx0 & ~31u;
     L.avail = L.fill;
+    L.rfill = L.rip = 0;   // (head_fill, rip_sync)
     L.ph = P_BHDR;
     L.st = ST_NOT_RUN;
     L.ip = L.op = L.fail_op = 0;
@@ -706,14 +782,18 @@ __device__ __forceinline__ bool lane_setup(Lane &L, const FrameDesc &d, bool act
 }
 
 // the 128 bytes from L.fill into the ring, synchronously
+template <class C>
 __device__ __forceinline__ void head_fill(Lane &L)
 {
+    L.rfill = C::kCarry ? C::Ring::of(L.fill) : 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const uint32_t fx = L.fill;
         const u32x4 a = bload16(L.cin, fx), b = bload16(L.cin, fx + 16);
-        ring_put(L, fx, a, b, true);
+        ring_put<C>(L, C::kCarry ? L.rfill : fx, a, b, true);
         L.fill += 32;
+        if (C::kCarry)
+            L.rfill = C::Ring::adv(L.rfill, 32);
     }
     L.avail = L.fill;
 }
@@ -728,7 +808,7 @@ __device__ __forceinline__ void head_fill(Lane &L)
 // BLK: the block route -- lane t parses job t of `jobs` (one LZ4 block from
 // its header at the job's speculative output offset, every liblz4 rule, up
 // to the next header) into the job's slots and result; n = the job slots.
-template <int DIAG, int D, bool BLK>
+template <class C, int DIAG, int D, bool BLK>
 __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))) void lz4_lean_kernel(
     const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ comp,
     const uint64_t *__restrict__ rec_base, uint64_t capacity, uint64_t *__restrict__ items,
@@ -736,7 +816,7 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
     uint32_t max_csize, uint32_t min_csize, const BlockJob *__restrict__ jobs, BlockRes *__restrict__ jres,
     const uint32_t *__restrict__ njobs)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t rings[kLW * 64 * kStride];
+    __shared__ __attribute__((aligned(16))) uint8_t rings[kLW * 64 * C::kStride];
     __shared__ __attribute__((aligned(16))) uint64_t tabs[kLW * (kFlush + 1)];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t tab = (uint32_t)(uintptr_t)(tabs) + (threadIdx.x >> 6) * 8 * (kFlush + 1);
@@ -776,7 +856,9 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
     if (clo == ~0ull)
         return;   // no frame in this wave (inactive lanes stay: flushes take all 64)
     Lane L;
-    L.ring = (uint32_t)(uintptr_t)(rings) + threadIdx.x * kStride;
+    static_assert(!C::kWaveSink, "the single-wave kernel keeps a sink per lane");
+    L.ring = (uint32_t)(uintptr_t)(rings) + threadIdx.x * C::kStride;
+    L.sink = L.ring + C::kSink;
     if (!lane_setup(L, d, act, rb0, cap, comp, items, capacity, clo, chi, ilo, ihi)) {
         finish(L, ST_NOT_RUN);
     } else if (BLK) {
@@ -789,23 +871,24 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
         L.indep = (J.info >> 8) & 1;
         L.max_block = 1u << (8 + 2 * L.bsid);
         L.fill = (L.cx0 + J.hpos) & ~31u;
-        head_fill(L);
+        head_fill<C>(L);
+        rip_sync<C>(L);
     } else {
         // frame header: the first 128 bytes, synchronously
-        head_fill(L);
-        const int32_t hs = hdr_status(L);
+        head_fill<C>(L);
+        const int32_t hs = hdr_status<C>(L);
         if (hs >= 0)
             finish(L, hs);
     }
-    Fill sl[D];
+    Fill<C::kPieces> sl[D];
 #pragma unroll
     for (int i = 0; i < D; i++) {
         sl[i].x = kOff;
-        sl[i].h2 = false;
+        sl[i].rx = sl[i].n = 0;
     }
     uint32_t rounds = 0, fcnt = 0;
     // the table's sink entry names a valid line from the start
-    *lp<uint64_t>(tab + 8 * kFlush) = L.ring + kIBuf;
+    *lp<uint64_t>(tab + 8 * kFlush) = L.ring + C::kIBuf;
     wave_lds_sync();
     for (;;) {
         // two sub-steps per slot: the first retires and refills it, the
@@ -815,14 +898,14 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
         if (DIAG & 64) {
 #pragma unroll
             for (int i = 0; i < D; i += 2) {
-                sub<false, true, DIAG>(L, sl[i], lane, tab, fcnt);
-                sub<true, true, DIAG>(L, sl[i + 1], lane, tab, fcnt);
+                sub<C, false, true, DIAG>(L, sl[i], lane, tab, fcnt);
+                sub<C, true, true, DIAG>(L, sl[i + 1], lane, tab, fcnt);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < D; i++) {
-                sub<false, true, DIAG>(L, sl[i], lane, tab, fcnt);
-                sub<true, false, DIAG>(L, sl[i], lane, tab, fcnt);
+                sub<C, false, true, DIAG>(L, sl[i], lane, tab, fcnt);
+                sub<C, true, false, DIAG>(L, sl[i], lane, tab, fcnt);
             }
         }
         const bool busy = L.ph != P_DONE;
@@ -844,10 +927,10 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
     // the items not yet flushed: pairs of slots from the buffer (a pair past
     // k holds garbage in a slot below cap)
     for (uint32_t x = L.kf; x < L.k; x += 2) {
-        const uint32_t a = L.ring + kIBuf + 8 * (x & 31);
+        const uint32_t a = L.ring + C::kIBuf + 8 * (x & 31);
         const u32x4 v = (u32x4){lp<uint32_t>(a)[0], lp<uint32_t>(a)[1],
-                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[0],
-                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[1]};
+                                lp<uint32_t>(L.ring + C::kIBuf + 8 * ((x + 1) & 31))[0],
+                                lp<uint32_t>(L.ring + C::kIBuf + 8 * ((x + 1) & 31))[1]};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), L.irs, 8 * (L.ib + x), 0, 0);
     }
     if ((DIAG & 4) && act) {
@@ -885,7 +968,7 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
 // only grows, so a stale one is smaller than the truth, which is the safe
 // side of each rule below.  Nothing depends on which SIMD a wave runs on.
 //
-//   (1) The mover writes ring bytes only below need_x_seen + kRing - 16
+//   (1) The mover writes ring bytes only below need_x_seen + R - 16
 //       (fill_issue's limit).  need_x_seen <= the parser's ip and the parser
 //       reads only coordinates >= ip, so no unread byte is overwritten.
 //   (2) After a jump avail restarts at the new fill position, which is
@@ -898,8 +981,14 @@ __global__ __launch_bounds__(64 * kLW) __attribute__((amdgpu_waves_per_eu(1, 1))
 //   (4) The mover hands a line over only when k_seen - kf >= 16: all 16
 //       slots of it were written before that k was published.
 constexpr uint32_t kDone = 0x80000000u;
-constexpr uint32_t kPairLds = kLW * 64 * kStride + kLW * 8 * (kFlush + 1) + kLW * 64 * 16;
-static_assert(kPairLds <= 160 * 1024, "the pair parse's LDS exceeds a CU's 160 KB");
+// the workgroup's LDS: lane areas, the movers' flush tables, mailboxes, and a
+// 32-byte sink per wave (used where the lane areas hold none)
+template <class C>
+constexpr uint32_t pair_lds()
+{
+    return kLW * 64 * C::kStride + kLW * 8 * (kFlush + 1) + kLW * 64 * 16 + 2 * kLW * 32;
+}
+static_assert(pair_lds<PairCfg>() <= 160 * 1024, "the pair parse's LDS exceeds a CU's 160 KB");
 
 __device__ __forceinline__ void mail_put(uint32_t a, uint32_t lo, uint32_t hi)
 {
@@ -913,7 +1002,7 @@ __device__ __forceinline__ uint64_t mail_get(uint32_t a)
 
 // One parser sub-step: up to two sequences against the mailbox's avail and
 // kf, the exact step where some lane needs it, then the new need_x and k.
-template <bool SLOW, bool STATS>
+template <class C, bool SLOW, bool STATS>
 __device__ __forceinline__ void parser_sub(Lane &L, uint32_t mp, uint32_t mm)
 {
     const uint64_t m = mail_get(mm);
@@ -921,7 +1010,7 @@ __device__ __forceinline__ void parser_sub(Lane &L, uint32_t mp, uint32_t mm)
     L.kf = (uint32_t)(m >> 32);
     u32x4 dv;
     const bool live = L.ph != P_DONE;
-    const bool need = fast<false>(L, 0, 0, dv);
+    const bool need = fast<C, false>(L, 0, 0, dv);
     const bool e1 = L.nk != 0;
     if (STATS) {
         L.cnt[0] += live;
@@ -933,17 +1022,19 @@ __device__ __forceinline__ void parser_sub(Lane &L, uint32_t mp, uint32_t mm)
     if (SLOW && __builtin_expect(__ballot(need) != 0, 0)) {
         if (STATS)
             L.cnt[8] += 1;
-        if (need)
-            slow(L);
+        if (need) {
+            slow<C>(L);
+            rip_sync<C>(L);
+        }
     }
-    put_items(L);   // rule (3)
-    (void)fast<false>(L, 0, 0, dv);
+    put_items<C>(L);   // rule (3)
+    (void)fast<C, false>(L, 0, 0, dv);
     if (STATS) {
         L.cnt[2] += L.nk != 0;
         L.cnt[6] += e1 && L.nk == 0 && (L.why & 1);
         L.cnt[7] += e1 && L.nk == 0 && (L.why & 128);
     }
-    put_items(L);
+    put_items<C>(L);
     mail_put(mp, L.cx0 + L.ip, L.k | (L.ph == P_DONE ? kDone : 0u));
 }
 
@@ -951,8 +1042,8 @@ __device__ __forceinline__ void parser_sub(Lane &L, uint32_t mp, uint32_t mm)
 // read the lines handed over last sub-step, publish avail and kf, store the
 // lines, hand over new ones, issue S's next loads (FILL).  L.k and done are
 // the parser's as last seen.
-template <bool FILL>
-__device__ __forceinline__ void mover_sub(Lane &L, Fill &S, bool &done, uint32_t lane, uint32_t tab,
+template <class C, bool FILL>
+__device__ __forceinline__ void mover_sub(Lane &L, Fill<C::kPieces> &S, bool &done, uint32_t lane, uint32_t tab,
                                           uint32_t mp, uint32_t mm, uint32_t &fcnt)
 {
     const uint64_t m = mail_get(mp);
@@ -960,7 +1051,7 @@ __device__ __forceinline__ void mover_sub(Lane &L, Fill &S, bool &done, uint32_t
     L.k = (uint32_t)(m >> 32) & ~kDone;
     done = (m >> 63) != 0;
     if (FILL)
-        fill_retire(L, S);
+        fill_retire<C>(L, S);
     const uint32_t g = lane >> 3, pc = lane & 7;
     const uint64_t fe = *lp<uint64_t>(tab + 8 * (g < fcnt ? g : kFlush));
     const u32x4 fv = *lp<u32x4>((uint32_t)fe + 16 * pc);
@@ -968,25 +1059,29 @@ __device__ __forceinline__ void mover_sub(Lane &L, Fill &S, bool &done, uint32_t
     mail_put(mm, L.avail, L.kf);   // rule (3): L.kf counts lines read by now
     flush_store<0>(L, fe, fv, g, pc, fcnt);
     wave_lds_sync();
-    fcnt = flush_hand(L, tab);   // rule (4)
+    fcnt = flush_hand<C>(L, tab);   // rule (4)
     wave_lds_sync();
     if (FILL)
-        fill_issue(L, S, need_x, !done);   // rule (1)
+        fill_issue<C>(L, S, need_x, !done);   // rule (1)
 }
 
 // EVERY: every mover sub-step retires and refills a slot (else every other
-// one, the single-wave kernel's cadence); D: fill pipeline depth.
-template <bool EVERY, int D, bool STATS>
+// one, the single-wave kernel's cadence); D: fill pipeline depth; C: the ring
+// length, the slot width and where the sink is.
+template <class C, bool EVERY, int D, bool STATS>
 __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2))) void lz4_lean_pair_kernel(
     const FrameDesc *__restrict__ desc, uint32_t n, const uint8_t *__restrict__ comp,
     const uint64_t *__restrict__ rec_base, uint64_t capacity, uint64_t *__restrict__ items,
     uint32_t *__restrict__ nitems, int32_t *__restrict__ status, uint32_t *__restrict__ fail_at,
     uint32_t max_csize, uint32_t min_csize)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t rings[kLW * 64 * kStride];
+    __shared__ __attribute__((aligned(16))) uint8_t rings[kLW * 64 * C::kStride];
     __shared__ __attribute__((aligned(16))) uint64_t tabs[kLW * (kFlush + 1)];
     __shared__ __attribute__((aligned(16))) uint64_t mail_p[kLW * 64], mail_m[kLW * 64];
-    static_assert(sizeof(rings) + sizeof(tabs) + sizeof(mail_p) + sizeof(mail_m) == kPairLds, "LDS layout");
+    __shared__ __attribute__((aligned(16))) uint8_t sinks[2 * kLW * 32];
+    static_assert(sizeof(rings) + sizeof(tabs) + sizeof(mail_p) + sizeof(mail_m) + sizeof(sinks) == pair_lds<C>(),
+                  "LDS layout");
+    static_assert(pair_lds<C>() <= 160 * 1024, "the pair parse's LDS exceeds a CU's 160 KB");
     constexpr int kPD = 2;   // parser rounds of 2 * kPD sub-steps, as the single-wave kernel's at D = 2
     const uint32_t t = threadIdx.x & (64 * kLW - 1), lane = threadIdx.x & 63;
     const bool mover = uni(threadIdx.x) >= 64 * kLW;   // waves 4-7
@@ -1016,7 +1111,8 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
     // stays for both barriers
     const bool some = clo != ~0ull;
     Lane L;
-    L.ring = (uint32_t)(uintptr_t)(rings) + t * kStride;
+    L.ring = (uint32_t)(uintptr_t)(rings) + t * C::kStride;
+    L.sink = C::kWaveSink ? (uint32_t)(uintptr_t)(sinks) + (threadIdx.x >> 6) * 32 : L.ring + C::kSink;
     bool ok = false;
     if (some) {
         ok = lane_setup(L, d, act, rb0, cap, comp, items, capacity, clo, chi, ilo, ihi);
@@ -1025,7 +1121,7 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (mover) {
             // frame header: the first 128 bytes, synchronously
             if (ok)
-                head_fill(L);
+                head_fill<C>(L);
             mail_put(mm, L.avail, 0);
         } else {
             mail_put(mp, L.cx0, ok ? 0u : kDone);
@@ -1033,23 +1129,23 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
     __syncthreads();
     if (some && mover) {
-        Fill sl[D];
+        Fill<C::kPieces> sl[D];
 #pragma unroll
         for (int i = 0; i < D; i++) {
             sl[i].x = kOff;
-            sl[i].h2 = false;
+            sl[i].rx = sl[i].n = 0;
         }
         uint32_t rounds = 0, fcnt = 0;
         bool done = !ok;
         // the table's sink entry names a valid line from the start
-        *lp<uint64_t>(tab + 8 * kFlush) = L.ring + kIBuf;
+        *lp<uint64_t>(tab + 8 * kFlush) = L.ring + C::kIBuf;
         wave_lds_sync();
         for (;;) {
 #pragma unroll
             for (int i = 0; i < D; i++) {
-                mover_sub<true>(L, sl[i], done, lane, tab, mp, mm, fcnt);
+                mover_sub<C, true>(L, sl[i], done, lane, tab, mp, mm, fcnt);
                 if (!EVERY)
-                    mover_sub<false>(L, sl[i], done, lane, tab, mp, mm, fcnt);
+                    mover_sub<C, false>(L, sl[i], done, lane, tab, mp, mm, fcnt);
             }
             // until every lane is done and has no complete line left; bounded
             // like the parser's loop, plus the rounds the pipeline may lag it
@@ -1066,7 +1162,7 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
     } else if (some) {
         L.avail = (uint32_t)mail_get(mm);
         if (ok) {
-            const int32_t hs = hdr_status(L);
+            const int32_t hs = hdr_status<C>(L);
             if (hs >= 0)
                 finish(L, hs);
         }
@@ -1076,8 +1172,8 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
             // exact step
 #pragma unroll
             for (int i = 0; i < kPD; i++) {
-                parser_sub<false, STATS>(L, mp, mm);
-                parser_sub<true, STATS>(L, mp, mm);
+                parser_sub<C, false, STATS>(L, mp, mm);
+                parser_sub<C, true, STATS>(L, mp, mm);
             }
             const bool busy = L.ph != P_DONE;
             if (!__any(busy))
@@ -1098,10 +1194,10 @@ __global__ __launch_bounds__(128 * kLW) __attribute__((amdgpu_waves_per_eu(2, 2)
     // pair past k holds garbage in a slot below cap)
     const uint32_t kf = (uint32_t)(mail_get(mm) >> 32);
     for (uint32_t x = kf; x < L.k; x += 2) {
-        const uint32_t a = L.ring + kIBuf + 8 * (x & 31);
+        const uint32_t a = L.ring + C::kIBuf + 8 * (x & 31);
         const u32x4 v = (u32x4){lp<uint32_t>(a)[0], lp<uint32_t>(a)[1],
-                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[0],
-                                lp<uint32_t>(L.ring + kIBuf + 8 * ((x + 1) & 31))[1]};
+                                lp<uint32_t>(L.ring + C::kIBuf + 8 * ((x + 1) & 31))[0],
+                                lp<uint32_t>(L.ring + C::kIBuf + 8 * ((x + 1) & 31))[1]};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), L.irs, 8 * (L.ib + x), 0, 0);
     }
     status[f] = L.st;
@@ -1124,23 +1220,48 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
         return 0;
     const uint32_t per = 64 * kLW;
     const dim3 grid((nframes + per - 1) / per);
-#define ZSK_PAIR(E, P, S)                                                                                       \
-    hipLaunchKernelGGL((lz4_lean_pair_kernel<E, P, S>), grid, dim3(2 * per), 0, stream, d_desc, nframes, d_comp, \
+#define ZSK_PAIR(C, E, P, S)                                                                                       \
+    hipLaunchKernelGGL((lz4_lean_pair_kernel<C, E, P, S>), grid, dim3(2 * per), 0, stream, d_desc, nframes, d_comp, \
                        rec_base, capacity, items, nitems, d_status, d_fail_at, max_csize, min_csize)
 #ifdef ZSK_TUNING
 #define ZSK_LEAN(D, P)                                                                                         \
-    hipLaunchKernelGGL((lz4_lean_kernel<D, P, false>), grid, dim3(per), 0, stream, d_desc, nframes, d_comp, rec_base, \
-                       capacity, items, nitems, d_status, d_fail_at, max_csize, min_csize, nullptr, nullptr,       \
-                       nullptr)
+    hipLaunchKernelGGL((lz4_lean_kernel<BlockCfg, D, P, false>), grid, dim3(per), 0, stream, d_desc, nframes, d_comp, \
+                       rec_base, capacity, items, nitems, d_status, d_fail_at, max_csize, min_csize, nullptr,      \
+                       nullptr, nullptr)
     // bit 128: the single-wave kernel (as the block route runs it), its
     // diagnostics in the other bits.  Without it the pair kernel: 64 = every
     // mover sub-step fills, 8 = a 4-deep fill pipeline, 4 = sub-step counters
-    // (printed)
+    // (printed); bits 16 / 32 = a ring of 288 / 320 bytes (else 256), bit 1 =
+    // 96-byte, bit 2 = 128-byte fill slots (else 64) -- at the kept cadence only
     if (!(diag & 128)) {
+        using R256 = Cfg<256, 64, false>;
+        using R256w = Cfg<256, 96, false>;
+        using R288 = Cfg<288, 64, false>;
+        using R288w = Cfg<288, 96, false>;
+        using R320 = Cfg<320, 64, true>;
+        using R320w = Cfg<320, 96, true>;
+        using R256x = Cfg<256, 128, false>;
+        using R320x = Cfg<320, 128, true>;
+        const int ring = diag & 0x33;
         if (diag & 4) {
             unsigned long long z[kLeanStats] = {0};
             (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_lean_stats), z, sizeof(z), 0, hipMemcpyHostToDevice, stream);
-            ZSK_PAIR(false, 2, true);
+            if (ring == 0x01)
+                ZSK_PAIR(R256w, false, 2, true);
+            else if (ring == 0x10)
+                ZSK_PAIR(R288, false, 2, true);
+            else if (ring == 0x11)
+                ZSK_PAIR(R288w, false, 2, true);
+            else if (ring == 0x20)
+                ZSK_PAIR(R320, false, 2, true);
+            else if (ring == 0x21)
+                ZSK_PAIR(R320w, false, 2, true);
+            else if (ring == 0x02)
+                ZSK_PAIR(R256x, false, 2, true);
+            else if (ring == 0x22)
+                ZSK_PAIR(R320x, false, 2, true);
+            else
+                ZSK_PAIR(R256, false, 2, true);
             (void)hipMemcpyFromSymbolAsync(z, HIP_SYMBOL(g_lean_stats), sizeof(z), 0, hipMemcpyDeviceToHost, stream);
             (void)hipStreamSynchronize(stream);
             const double fr = nframes;
@@ -1148,14 +1269,28 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
                             "waits: bytes %.1f flush %.1f exact-needed %.1f; second misses after a first: bytes %.1f "
                             "flush %.1f; exact-step runs %.1f\n", z[0] / fr, z[1] / fr, z[2] / fr, z[3] / fr, z[4] / fr,
                     z[5] / fr, z[6] / fr, z[7] / fr, z[8] / fr);
-        } else if ((diag & 72) == 72)
-            ZSK_PAIR(true, 4, false);
+        } else if (ring == 0x01)
+            ZSK_PAIR(R256w, false, 2, false);
+        else if (ring == 0x10)
+            ZSK_PAIR(R288, false, 2, false);
+        else if (ring == 0x11)
+            ZSK_PAIR(R288w, false, 2, false);
+        else if (ring == 0x20)
+            ZSK_PAIR(R320, false, 2, false);
+        else if (ring == 0x21)
+            ZSK_PAIR(R320w, false, 2, false);
+        else if (ring == 0x02)
+            ZSK_PAIR(R256x, false, 2, false);
+        else if (ring == 0x22)
+            ZSK_PAIR(R320x, false, 2, false);
+        else if ((diag & 72) == 72)
+            ZSK_PAIR(R256, true, 4, false);
         else if (diag & 64)
-            ZSK_PAIR(true, 2, false);
+            ZSK_PAIR(R256, true, 2, false);
         else if (diag & 8)
-            ZSK_PAIR(false, 4, false);
+            ZSK_PAIR(R256, false, 4, false);
         else
-            ZSK_PAIR(false, 2, false);
+            ZSK_PAIR(R256, false, 2, false);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (diag & 4) {
@@ -1190,7 +1325,7 @@ int launch_lz4_lean(const FrameDesc *d_desc, uint32_t nframes, const uint8_t *d_
 #undef ZSK_LEAN
 #else
     (void)diag;
-    ZSK_PAIR(false, 2, false);
+    ZSK_PAIR(PairCfg, false, 2, false);
 #endif
 #undef ZSK_PAIR
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1205,7 +1340,7 @@ int launch_lz4_lean_blocks(const FrameDesc *d_desc, const uint8_t *d_comp, const
     if (lanes > s->jobs_cap || !s->jobs || !s->jres || !s->njobs)
         return -1;
     const uint32_t per = 64 * kLW;
-    hipLaunchKernelGGL((lz4_lean_kernel<0, 2, true>), dim3((lanes + per - 1) / per), dim3(per), 0, stream,
+    hipLaunchKernelGGL((lz4_lean_kernel<BlockCfg, 0, 2, true>), dim3((lanes + per - 1) / per), dim3(per), 0, stream,
                        d_desc, lanes, d_comp, rec_base, capacity, items, nullptr, nullptr, nullptr, 0u,
                        min_jobs, s->jobs, s->jres, s->njobs);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -85,7 +85,12 @@ int overlapped(uint32_t K, const FrameDesc *d_desc, uint32_t nframes, const uint
 //   0x2xx      plan + lean parse with diagnostic bits xx (lz4_lean.hip): 0x200
 //              the pair kernel, 0x280 the single-wave kernel, 0x240 / 0x208 /
 //              0x248 the pair kernel's fill cadences; 0x204 / 0x284 print
-//              the pair / single-wave sub-step counters
+//              the pair / single-wave sub-step counters; the pair kernel's
+//              ring variants: + 0x10 / 0x20 a ring of 288 / 320 bytes, + 0x01 /
+//              0x02 96- / 128-byte fill slots (0x200 ... 0x222, with 0x04
+//              their counters)
+//   0x9xx      the whole decode with the lean parse's diagnostic bits xx: the
+//              ring variants' output is complete (kbench checks it bit-exact)
 //   0x50K      plan, then K frame chunks, chunk c + 1's lean parse on a
 //              second stream beside chunk c's execute (0x501 = no overlap)
 //   0x400      execute alone with round 0 direct (copy_direct); 0x401 the
@@ -112,6 +117,8 @@ int launch_lz4_frames_variant(int variant, const FrameDesc *d_desc, uint32_t nfr
         return staged(4, ROUTE_AUTO, (variant & 0x3FF) << 8, d_desc, nframes, d_comp, d_out, d_status, stream);
     if ((variant & 0xF00) == 0x200)
         return staged(3, ROUTE_LEAN, variant & 0xFF, d_desc, nframes, d_comp, d_out, d_status, stream);
+    if ((variant & 0xF00) == 0x900)
+        return staged(15, ROUTE_LEAN, variant & 0xFF, d_desc, nframes, d_comp, d_out, d_status, stream);
     if (variant == 0x400)   // execute alone, round 0 direct (seq_exec.hip copy_direct)
         return staged(4, ROUTE_AUTO, 0x400 << 8, d_desc, nframes, d_comp, d_out, d_status, stream);
     if (variant == 0x401)   // the whole decode with it
