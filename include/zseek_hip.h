@@ -756,9 +756,39 @@ ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *d_desc,
  * refused with c_size 0 and its slot untouched, the same bytes on every run,
  * ZSK_COMPRESS_CONTENT_CHECKSUM honoured.  An unknown @format returns -1 (0
  * from the scratch size) and queues nothing.
+ *
+ * ZSK_ZSTD_FORMAT_FULL_WIDE (csrc/zstd_enc_wide_dev.h; ZSK_ZSTD_FORMAT_FULL | 4,
+ * bit 2 selecting the search) is the full format over a wider match search;
+ * the format layer -- header, blocks, block-type rule, literals, table modes,
+ * repeat offsets, checksum -- is the full format's, only the sequences handed
+ * to it differ:
+ *   n <= 16384  the full format's search (hash log 12, a table per block): the
+ *               frame is ZSK_ZSTD_FORMAT_FULL's frame byte for byte.
+ *   n >  16384  h = (v * 2654435761u) >> (32 - 14) over the 4 bytes v at a
+ *               position; one table of 2^14 entries holding position + 1
+ *               relative to the frame's start (0: empty), zeroed once, at the
+ *               frame's start.  Block b's search is the full format's -- 64
+ *               positions a step; the lowest position whose candidate's 4
+ *               bytes match wins; the match extends to at most the block's own
+ *               end; the step's positions below the next step's start enter
+ *               the table, the highest one on a clash -- over the table as the
+ *               earlier blocks' searches left it.  A candidate may lie in any
+ *               earlier block and an offset may reach n - 1; a match never
+ *               passes the end of its own block, its source may run across a
+ *               block boundary.  A searched block's positions enter the table
+ *               whether it is written Compressed or Raw; an empty block or a
+ *               block of one repeated byte is not searched and inserts
+ *               nothing.  The repeat-offset history rule is unchanged.
+ * The contract is the full format's whole.  The scratch grows by the tables,
+ * 64 KiB per resident workgroup (at most 1,792): 576 KiB instead of 512 KiB
+ * per frame of a batch, at most 1,008 MiB instead of 896 MiB; a @d_scratch
+ * below zsk_zstd_compress_scratch_size_ex(.., ZSK_ZSTD_FORMAT_FULL_WIDE), or
+ * one that is not 16-byte aligned, returns -1.  The subset's and the full
+ * format's sizes are what they were.  Formats 2, 3 and 4 stay unknown.
  */
 #define ZSK_ZSTD_FORMAT_SUBSET 0   /* zsk_zstd_compress_frames' frames, byte for byte */
 #define ZSK_ZSTD_FORMAT_FULL   1
+#define ZSK_ZSTD_FORMAT_FULL_WIDE 5   /* the full format over the frame-wide match search */
 ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size_ex(uint32_t nframes, uint64_t src_bytes, int format);
 ZSEEK_EXPORT int zsk_zstd_compress_frames_ex(const zsk_compress_desc_t *d_desc,
     uint32_t nframes, const void *d_src, void *d_dst, uint32_t *d_csize,
@@ -923,15 +953,20 @@ ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t f
  * ZSK_IMAGE_CONTENT_CHECKSUMS: the same XXH64 word (computed once) also ends
  * each frame.  ZSK_IMAGE_ZSTD_FULL: the frames in ZSK_ZSTD_FORMAT_FULL (the
  * bounds and the scratch are the same; zsk_lz4_build_image ignores the bit).
+ * ZSK_IMAGE_ZSTD_WIDE: the frames in ZSK_ZSTD_FORMAT_FULL_WIDE, with or
+ * without ZSK_IMAGE_ZSTD_FULL, which it implies (the bounds are the same, the
+ * scratch grows by the search's tables; zsk_lz4_build_image ignores the bit).
  * @batch_bytes 0: 256 MiB.  zsk_zstd_image_bound: every frame at
  * its bound plus the table; 0 for frame_size == 0.  Errors are
  * zsk_lz4_build_image's, under the same conditions (there is no level).  The
  * result is read as zstd by the reference reader and zsk_reader_open_device.
  * The pooled scratch is zsk_lz4_build_image's with the zstd compressor's in
- * place of the LZ4 tables: 512 KiB per frame of a batch, at most 896 MiB.
+ * place of the LZ4 tables: 512 KiB per frame of a batch, at most 896 MiB;
+ * with ZSK_IMAGE_ZSTD_WIDE 576 KiB per frame of a batch, at most 1,008 MiB.
  */
 #define ZSK_IMAGE_CONTENT_CHECKSUMS 2u
 #define ZSK_IMAGE_ZSTD_FULL 4u     /* zsk_zstd_build_image: frames in the full format */
+#define ZSK_IMAGE_ZSTD_WIDE 8u     /* zsk_zstd_build_image: the full format over the wide match search */
 ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_size, unsigned flags);
 ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size,
     unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,

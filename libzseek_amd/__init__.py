@@ -13,5 +13,6 @@ from .zseek import (  # noqa: F401
     zstd_seekable, zstd_tool_version, lz4_image_bound, lz4_build_image,
     zstd_compress_bound, zstd_compress_layout, zstd_compress_scratch_size, zstd_compress_frames,
     zstd_image_bound, zstd_build_image, ZSTD_FORMAT_SUBSET, ZSTD_FORMAT_FULL, IMAGE_ZSTD_FULL,
+    ZSTD_FORMAT_FULL_WIDE, IMAGE_ZSTD_WIDE,
     zstd_bounds_default, zstd_decode_frames_async, ERR_SCRATCH,
 )

@@ -197,12 +197,13 @@ struct Codec {
     uint64_t bound(uint64_t n) const { return zstd ? ZSK_ZSTD_COMPRESS_BOUND(n) : ZSK_LZ4_COMPRESS_BOUND(n); }
     size_t scratch(uint32_t nframes) const
     {
-        return zstd ? zstd_compress_scratch_size(nframes) : zsk_lz4_compress_scratch_size(nframes);
+        return zstd ? zstd_compress_scratch_size(nframes, format) : zsk_lz4_compress_scratch_size(nframes);
     }
 };
 constexpr Codec kLz4{false, ZSK_LZ4_COMPRESS_MAX_FRAME, 0},
     kZstd{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_SUBSET},
-    kZstdFull{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_FULL};
+    kZstdFull{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_FULL},
+    kZstdWide{true, ZSK_ZSTD_COMPRESS_MAX_FRAME, ZSK_ZSTD_FORMAT_FULL_WIDE};
 
 struct Geometry {
     uint64_t frames, full, tail, entry, bound;
@@ -406,6 +407,7 @@ extern "C" ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_siz
 extern "C" ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size, unsigned flags,
                                                      size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
 {
-    return build_image((flags & ZSK_IMAGE_ZSTD_FULL) ? kZstdFull : kZstd, d_src, len, frame_size, 0, flags, batch_bytes,
-                       d_image, capacity, errbuf);
+    // (the wide search implies the full format)
+    const Codec &codec = (flags & ZSK_IMAGE_ZSTD_WIDE) ? kZstdWide : (flags & ZSK_IMAGE_ZSTD_FULL) ? kZstdFull : kZstd;
+    return build_image(codec, d_src, len, frame_size, 0, flags, batch_bytes, d_image, capacity, errbuf);
 }

@@ -507,8 +507,9 @@ int launch_src_checksums(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
 // contract).  d_sums: the frames' XXH64 low words when the caller already has
 // them (the image builder), nullptr to compute those the descriptors ask for
 // into the scratch.  format: ZSK_ZSTD_FORMAT_* (an unknown one: -1); the
-// scratch is the same for both.  Asynchronous on stream; 0 or -1.
-size_t zstd_compress_scratch_size(uint32_t nframes);
+// scratch is the same for the subset and the full format, the wide one adds
+// its tables.  Asynchronous on stream; 0 or -1.
+size_t zstd_compress_scratch_size(uint32_t nframes, int format);
 int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst,
                          uint32_t *d_csize, void *d_scratch, size_t scratch_size, const uint32_t *d_sums,
                          hipStream_t stream, int format);

@@ -1,7 +1,7 @@
 // zstd_compress.hip — zstd frame compression on the GPU (gfx950):
 // zsk_zstd_compress_frames and zsk_zstd_compress_frames_ex.  The frames are
 // valid zstd (RFC 8878) that libzstd decodes to the input; they are not
-// libzstd's bytes at any level, and there is one effort level.  Two formats,
+// libzstd's bytes at any level, and there is one effort level.  Three formats,
 // one kernel instantiation each, one launch per call:
 //   subset  zstd_enc_dev.h (shared with the CPU shim of tests/test_zstd_enc.py):
 //           everything that decides bytes once the matches are known.  It
@@ -12,12 +12,17 @@
 //           over all 256 byte values with the smaller of the two tree
 //           descriptions, a mode per sequence table and block, repeat offsets.
 //           Same match search, so the same sequences; see "full" below.
+//   wide    zstd_enc_wide_dev.h (tests/test_zstd_enc_wide.py's shim): the full
+//           format's layer over another search -- a frame above 16 KiB keeps
+//           one table of 2^14 positions, in the scratch, for all its blocks,
+//           so matches reach earlier blocks; see "wide" below.
 //
 // Mapping: one single-wave workgroup per frame, the frame's blocks (kZBlock
-// input bytes each) in order, each block independent of the others: a fresh
-// hash table, no matches into earlier blocks.  Workgroups are persistent (at
-// most kGridMax of them walk the batch), so the scratch -- a block's compacted
-// literals and its sequences -- is per workgroup, not per frame.
+// input bytes each) in order, each block independent of the others (but in
+// the wide format): a fresh hash table, no matches into earlier blocks.
+// Workgroups are persistent (at most kGridMax of them walk the batch), so the
+// scratch -- a block's compacted literals and its sequences, the wide format's
+// table -- is per workgroup, not per frame.
 //   match      the wave looks at 64 positions a step: every lane hashes the 4
 //              bytes at its position, reads the table (LDS, positions of
 //              earlier steps only) and compares; the lowest lane that matches
@@ -45,6 +50,17 @@
 //              chooses; bit sums, literal copy and the four streams are the
 //              subset's.  The frame's offset history sits in LDS and moves on
 //              only when a block is written Compressed.
+//   wide       the table of a frame above kWideMinFrame bytes is the
+//              workgroup's kWideTableBytes of global memory: cleared by the
+//              wave, whole, at the frame's start (a persistent workgroup's
+//              last frame must leave nothing: an entry past the new frame's
+//              length would be a read outside it), then block after block
+//              searched over it by the same find_matches, which reads it with
+//              global loads and enters positions by a global atomicMax.  An
+//              empty block or a one-byte run is written before the search and
+//              inserts nothing.  The index is a hash's top 14 bits; a
+//              candidate is an earlier position of the same frame.  Smaller
+//              frames take the full format's path and are its frames.
 // Source bytes are read only inside the frame (a 4-byte read always lies
 // within it); nothing is written outside the slot's ZSK_ZSTD_COMPRESS_BOUND.
 //
@@ -60,6 +76,7 @@
 #include "zsk_internal.h"
 #include "zstd_enc_dev.h"
 #include "zstd_enc_full_dev.h"
+#include "zstd_enc_wide_dev.h"
 
 namespace zsk {
 
@@ -121,6 +138,20 @@ struct LdsF {
 };
 static_assert(sizeof(PostF) <= sizeof(uint32_t) << kHashLog, "the block's work fits in the dead hash table");
 
+__host__ __device__ constexpr size_t align256(size_t v)
+{
+    return (v + 255) & ~(size_t)255;
+}
+
+// The scratch of a call: per workgroup the literals and sequences, then the
+// checksum kernel's descriptors and sums -- the subset's and full format's
+// whole scratch -- and behind that the wide format's tables, one per workgroup.
+__host__ __device__ constexpr size_t wide_tables_at(uint32_t grid, uint32_t nframes)
+{
+    return align256((size_t)grid * kWgScratch) + align256((size_t)nframes * sizeof(zsk_compress_desc_t)) +
+           align256((size_t)nframes * sizeof(uint32_t));
+}
+
 __device__ __forceinline__ uint32_t ld4(const uint8_t *p)
 {
     return *reinterpret_cast<const u32_ua *>(p);
@@ -139,6 +170,23 @@ __device__ __forceinline__ bool one_byte_run(const uint8_t *in, uint32_t n)
     return true;
 }
 
+// The wide search's table lies in global memory, and is addressed as such.
+typedef __attribute__((address_space(1))) uint32_t gu32;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// A position into the match search's table: the largest one stays.  In LDS for
+// the subset and full searches; in global memory for the wide one, where the
+// workgroup is one wave and owns its table, so only the lanes of one step
+// meet, and the barrier that ends the step orders it before the next reads.
+template <class TabT>
+__device__ __forceinline__ void tab_max(TabT *p, uint32_t v)
+{
+    if constexpr (std::is_same<TabT, gu32>::value)
+        __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else
+        atomicMax(p, v);
+}
+
 // Literals s[from, from + len) behind lit[nlit), counted: the subset in bins
 // 0..128 and one for the bytes above, the full format in 256.
 template <bool kFull>
@@ -154,9 +202,12 @@ __device__ __forceinline__ void take_literals(uint32_t *count, const uint8_t *s,
 
 // The match search of block s[b0, b0 + bn) (the file's head): the literals
 // compacted into lit and counted, the sequences into seq.  tab and count are
-// cleared by the caller; wave-uniform, and ends on a barrier.
-template <bool kFull>
-__device__ __forceinline__ void find_matches(uint32_t *tab, uint32_t *count, const uint8_t *__restrict__ s,
+// cleared by the caller; wave-uniform, and ends on a barrier.  The wide search
+// (kLog = kWideHashLog) is the same walk over the frame's table in global
+// memory, which the caller cleared at the frame's start: s is the frame, so
+// the positions are the frame's already.
+template <bool kFull, uint32_t kLog = kHashLog, class TabT = uint32_t>
+__device__ __forceinline__ void find_matches(TabT *tab, uint32_t *count, const uint8_t *__restrict__ s,
                                              uint32_t b0, uint32_t bn, uint8_t *__restrict__ lit,
                                              Seq *__restrict__ seq, uint32_t &nseq_out, uint32_t &nlit_out)
 {
@@ -168,14 +219,14 @@ __device__ __forceinline__ void find_matches(uint32_t *tab, uint32_t *count, con
         uint32_t v = 0, h = 0, cand = 0;
         if (valid) {
             v = ld4(s + pos);
-            h = match_hash(v);
+            h = kLog == kHashLog ? match_hash(v) : wide_hash(v);
             cand = tab[h];
         }
         const bool hit = valid && cand != 0 && ld4(s + cand - 1) == v;
         const uint64_t hits = __ballot(hit);
         if (hits == 0) {
             if (valid)
-                atomicMax(&tab[h], pos + 1);
+                tab_max(&tab[h], pos + 1);
             __syncthreads();
             base += 64;
             continue;
@@ -203,7 +254,7 @@ __device__ __forceinline__ void find_matches(uint32_t *tab, uint32_t *count, con
         }
         const uint32_t next = mpos + ml;
         if (valid && pos < next)
-            atomicMax(&tab[h], pos + 1);
+            tab_max(&tab[h], pos + 1);
         const uint32_t ll = mpos - anchor;
         take_literals<kFull>(count, s, anchor, ll, lit, nlit);
         if (lane == 0)
@@ -340,10 +391,18 @@ __device__ __forceinline__ Reps wave_offsets(Reps h, Seq *__restrict__ seq, uint
 // ... in the full format (zstd_enc_full_dev.h).  L.rep is the frame's offset
 // history before the block; a block written Compressed moves it on.  Kept out
 // of line: inlined into the frame loop it takes more than 256 VGPRs (hundreds
-// of SGPRs spilled into them); as a function it takes 84.
+// of SGPRs spilled into them); as a function it takes 84.  The wide kernel
+// (zstd_enc_wide_dev.h) passes one argument more, the full kernel none: the
+// frame's table (a gu32 *), or null for a frame the full search takes.  Only
+// the search differs: with a table, block s[b0, b0 + bn) is searched over it
+// as the earlier blocks left it -- an empty block or a one-byte run returns
+// before that and inserts nothing -- and the LDS table is only PostF's room.
+template <class... Tab>
 __device__ __noinline__ uint32_t compress_block(LdsF &L, const uint8_t *__restrict__ s, uint32_t b0, uint32_t bn, bool last,
-                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq)
+                                   uint8_t *__restrict__ dst, uint8_t *__restrict__ lit, Seq *__restrict__ seq,
+                                   Tab... tab)
 {
+    constexpr bool kWide = sizeof...(Tab) != 0;
     const uint32_t lane = threadIdx.x;
     if (bn == 0) {
         if (lane == 0)
@@ -357,15 +416,27 @@ __device__ __noinline__ uint32_t compress_block(LdsF &L, const uint8_t *__restri
         }
         return 4;
     }
-    for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
-        L.tab[i] = 0;
+    gu32 *wtab = nullptr;
+    if constexpr (kWide)
+        wtab = (tab, ...);
+    const bool wide = wtab != nullptr;
+    if (!wide)
+        for (uint32_t i = lane; i < (1u << kHashLog); i += 64)
+            L.tab[i] = 0;
     for (uint32_t i = lane; i < kHufSymsF; i += 64)
         L.count[i] = 0;
     if (lane < 4)
         L.bits[lane] = 0;
     __syncthreads();
     uint32_t nseq, nlit;   // ---- match
-    find_matches<true>(L.tab, L.count, s, b0, bn, lit, seq, nseq, nlit);
+    if constexpr (kWide) {
+        if (wide)
+            find_matches<true, kWideHashLog>(wtab, L.count, s, b0, bn, lit, seq, nseq, nlit);
+        else
+            find_matches<true>(L.tab, L.count, s, b0, bn, lit, seq, nseq, nlit);
+    } else {
+        find_matches<true>(L.tab, L.count, s, b0, bn, lit, seq, nseq, nlit);
+    }
     PostF &P = L.post;     // (the hash table is dead from here)
 
     // ---- offsets into offset values: serial in the history
@@ -465,7 +536,12 @@ __device__ __noinline__ uint32_t compress_block(LdsF &L, const uint8_t *__restri
 
 // One instantiation per format: the subset's is the kernel it was before the
 // full format existed, with its LDS, registers and seven workgroups per CU.
-template <bool kFull>
+// The wide one is the full kernel with a table of kWideTableBytes per workgroup
+// in the scratch, behind everything the others keep there (wide_tables_at).
+// The wave clears it at the start of every frame above kWideMinFrame bytes, all
+// of it, so a persistent workgroup's next frame finds nothing of the last one:
+// an entry at or past the new frame's length would be a read outside the frame.
+template <bool kFull, bool kWide = false>
 __global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_desc_t *__restrict__ desc,
                                                            uint32_t nframes, const uint8_t *__restrict__ src,
                                                            uint8_t *__restrict__ dst, uint32_t *__restrict__ csize,
@@ -502,9 +578,21 @@ __global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_de
         }
         uint32_t at = frame_header_size(n);
         const uint32_t nb = frame_blocks(n);
+        gu32 *wtab = nullptr;
+        if constexpr (kWide) {
+            if (wide_frame(n)) {
+                wtab = (gu32 *)(scratch + wide_tables_at(gridDim.x, nframes) + (size_t)blockIdx.x * kWideTableBytes);
+                auto *const t = (__attribute__((address_space(1))) u32x4 *)wtab;
+                for (uint32_t i = lane; i < kWideTableBytes / sizeof(u32x4); i += 64)
+                    t[i] = u32x4{0, 0, 0, 0};
+            }
+        }
         for (uint32_t b = 0; b < nb; b++) {
             const uint32_t b0 = b * kZBlock;
-            at += compress_block(L, s, b0, min(n - b0, kZBlock), b + 1 == nb, out + at, lit, seq);
+            if constexpr (kWide)
+                at += compress_block(L, s, b0, min(n - b0, kZBlock), b + 1 == nb, out + at, lit, seq, wtab);
+            else
+                at += compress_block(L, s, b0, min(n - b0, kZBlock), b + 1 == nb, out + at, lit, seq);
         }
         if (ck) {
             if (lane < 4)
@@ -515,6 +603,34 @@ __global__ __launch_bounds__(64) void zstd_compress_kernel(const zsk_compress_de
             csize[f] = at;
     }
 }
+
+}   // namespace
+
+// The wide instantiation lives in an object of its own: zstd_compress_wide.hip
+// is this file with ZSK_ZSTD_COMPRESS_WIDE_OBJECT defined, which leaves the
+// kernel's launch below and nothing else.  In one module the full and the wide
+// block encoders would share the format layer's functions, which are inlined
+// into a single caller but not into two, and the full kernel would no longer
+// be the code it was (130 VGPRs and 464 bytes of scratch for 84 and 352).
+void launch_zstd_compress_wide_kernel(uint32_t grid, hipStream_t stream, const zsk_compress_desc_t *d_desc,
+                                      uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst, uint32_t *d_csize,
+                                      const uint32_t *d_sums, uint8_t *d_scratch);
+
+#ifdef ZSK_ZSTD_COMPRESS_WIDE_OBJECT
+
+void launch_zstd_compress_wide_kernel(uint32_t grid, hipStream_t stream, const zsk_compress_desc_t *d_desc,
+                                      uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst, uint32_t *d_csize,
+                                      const uint32_t *d_sums, uint8_t *d_scratch)
+{
+    hipLaunchKernelGGL((zstd_compress_kernel<true, true>), dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src,
+                       d_dst, d_csize, d_sums, d_scratch);
+}
+
+}   // namespace zsk
+
+#else
+
+namespace {
 
 // The descriptors the checksum kernel sees: the frames that ask for a content
 // checksum, the others (and refused ones) as empty frames.
@@ -530,11 +646,6 @@ __global__ __launch_bounds__(256) void zstd_ckdesc_kernel(const zsk_compress_des
     out[i] = d;
 }
 
-size_t align256(size_t v)
-{
-    return (v + 255) & ~(size_t)255;
-}
-
 uint32_t grid_of(uint32_t nframes)
 {
     return std::min(nframes, kGridMax);
@@ -544,16 +655,17 @@ uint32_t grid_of(uint32_t nframes)
 
 bool zstd_format_known(int format)
 {
-    return format == ZSK_ZSTD_FORMAT_SUBSET || format == ZSK_ZSTD_FORMAT_FULL;
+    return format == ZSK_ZSTD_FORMAT_SUBSET || format == ZSK_ZSTD_FORMAT_FULL || format == ZSK_ZSTD_FORMAT_FULL_WIDE;
 }
 
-// (the same for both formats: what the full one adds lives in LDS)
-size_t zstd_compress_scratch_size(uint32_t nframes)
+// (the same for the subset and the full format: what the full one adds lives
+// in LDS; the wide format adds a table per resident workgroup)
+size_t zstd_compress_scratch_size(uint32_t nframes, int format)
 {
     if (nframes == 0)
         return 0;
-    return align256((size_t)grid_of(nframes) * kWgScratch) + align256((size_t)nframes * sizeof(zsk_compress_desc_t)) +
-           align256((size_t)nframes * sizeof(uint32_t));
+    const size_t base = wide_tables_at(grid_of(nframes), nframes);
+    return format == ZSK_ZSTD_FORMAT_FULL_WIDE ? base + (size_t)grid_of(nframes) * kWideTableBytes : base;
 }
 
 int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, const uint8_t *d_src, uint8_t *d_dst,
@@ -564,7 +676,10 @@ int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
         return -1;
     if (nframes == 0)
         return 0;
-    if (!d_desc || !d_src || !d_dst || !d_csize || !d_scratch || scratch_size < zstd_compress_scratch_size(nframes))
+    if (!d_desc || !d_src || !d_dst || !d_csize || !d_scratch ||
+        scratch_size < zstd_compress_scratch_size(nframes, format))
+        return -1;
+    if (format == ZSK_ZSTD_FORMAT_FULL_WIDE && ((uintptr_t)d_scratch & 15))   // (the tables: 16-byte stores)
         return -1;
     const uint32_t grid = grid_of(nframes);
     uint8_t *const wg = static_cast<uint8_t *>(d_scratch);
@@ -578,7 +693,9 @@ int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
             return -1;
         d_sums = sums;
     }
-    if (format == ZSK_ZSTD_FORMAT_FULL)
+    if (format == ZSK_ZSTD_FORMAT_FULL_WIDE)
+        launch_zstd_compress_wide_kernel(grid, stream, d_desc, nframes, d_src, d_dst, d_csize, d_sums, wg);
+    else if (format == ZSK_ZSTD_FORMAT_FULL)
         hipLaunchKernelGGL(zstd_compress_kernel<true>, dim3(grid), dim3(64), 0, stream, d_desc, nframes, d_src, d_dst,
                            d_csize, d_sums, wg);
     else
@@ -592,7 +709,7 @@ int launch_zstd_compress(const zsk_compress_desc_t *d_desc, uint32_t nframes, co
 extern "C" ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size(uint32_t nframes, uint64_t src_bytes)
 {
     (void)src_bytes;   // the scratch is per resident workgroup and per frame, not per input byte
-    return zsk::zstd_compress_scratch_size(nframes);
+    return zsk::zstd_compress_scratch_size(nframes, ZSK_ZSTD_FORMAT_SUBSET);
 }
 
 extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *d_desc, uint32_t nframes,
@@ -607,7 +724,7 @@ extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames(const zsk_compress_desc_t *
 extern "C" ZSEEK_EXPORT size_t zsk_zstd_compress_scratch_size_ex(uint32_t nframes, uint64_t src_bytes, int format)
 {
     (void)src_bytes;
-    return zsk::zstd_format_known(format) ? zsk::zstd_compress_scratch_size(nframes) : 0;
+    return zsk::zstd_format_known(format) ? zsk::zstd_compress_scratch_size(nframes, format) : 0;
 }
 
 extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames_ex(const zsk_compress_desc_t *d_desc, uint32_t nframes,
@@ -619,3 +736,5 @@ extern "C" ZSEEK_EXPORT int zsk_zstd_compress_frames_ex(const zsk_compress_desc_
                                      static_cast<uint8_t *>(d_dst), d_csize, d_scratch, scratch_size, nullptr,
                                      static_cast<hipStream_t>(stream), format);
 }
+
+#endif   // ZSK_ZSTD_COMPRESS_WIDE_OBJECT

@@ -997,25 +997,31 @@ def zstd_compress_layout(sizes, src_offsets=None, flags=None) -> tuple[np.ndarra
 
 ZSTD_FORMAT_SUBSET = 0   # ZSK_ZSTD_FORMAT_SUBSET
 ZSTD_FORMAT_FULL = 1     # ZSK_ZSTD_FORMAT_FULL
+ZSTD_FORMAT_FULL_WIDE = 5   # ZSK_ZSTD_FORMAT_FULL_WIDE
 
 
-def zstd_compress_scratch_size(nframes: int, src_bytes: int = 0, full: bool = False) -> int:
+def zstd_compress_scratch_size(nframes: int, src_bytes: int = 0, full: bool = False, wide: bool = False) -> int:
+    """wide=True (which implies the full format): ZSK_ZSTD_FORMAT_FULL_WIDE's larger scratch."""
+    if wide:
+        return int(lib().zsk_zstd_compress_scratch_size_ex(nframes, src_bytes, ZSTD_FORMAT_FULL_WIDE))
     if not full:
         return int(lib().zsk_zstd_compress_scratch_size(nframes, src_bytes))
     return int(lib().zsk_zstd_compress_scratch_size_ex(nframes, src_bytes, ZSTD_FORMAT_FULL))
 
 
-def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None = None, full: bool = False) -> None:
+def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None = None, full: bool = False,
+                         wide: bool = False) -> None:
     """zsk_zstd_compress_frames on torch device tensors (async on the current
     stream): desc = COMPRESS_DESC_DTYPE bytes (uint8), src / dst uint8,
     csize one int32 per frame (frame sizes out; 0 = refused descriptor).
-    full=True: zsk_zstd_compress_frames_ex with ZSK_ZSTD_FORMAT_FULL."""
+    full=True: zsk_zstd_compress_frames_ex with ZSK_ZSTD_FORMAT_FULL;
+    wide=True: with ZSK_ZSTD_FORMAT_FULL_WIDE (which implies full)."""
     import torch
     n = csize.numel()
     if desc.numel() != n * 24:
         raise ValueError("desc must hold 24 bytes per frame")
     if scratch is None:
-        scratch = torch.empty(max(zstd_compress_scratch_size(n, src.numel(), full), 1), dtype=torch.uint8,
+        scratch = torch.empty(max(zstd_compress_scratch_size(n, src.numel(), full, wide), 1), dtype=torch.uint8,
                               device=csize.device)
     for t in (desc, src, dst, csize, scratch):
         if not t.is_cuda or not t.is_contiguous():
@@ -1024,18 +1030,22 @@ def zstd_compress_frames(desc, src, dst, csize, scratch=None, stream: int | None
         stream = torch.cuda.current_stream().cuda_stream
     args = (desc.data_ptr(), n, src.data_ptr(), dst.data_ptr(), csize.data_ptr(), scratch.data_ptr(),
             scratch.numel(), stream)
-    r = lib().zsk_zstd_compress_frames_ex(*args, ZSTD_FORMAT_FULL) if full else lib().zsk_zstd_compress_frames(*args)
+    if wide:
+        r = lib().zsk_zstd_compress_frames_ex(*args, ZSTD_FORMAT_FULL_WIDE)
+    else:
+        r = lib().zsk_zstd_compress_frames_ex(*args, ZSTD_FORMAT_FULL) if full else lib().zsk_zstd_compress_frames(*args)
     if r != 0:
         raise ZseekError("zsk_zstd_compress_frames launch failed")
 
 
 IMAGE_CONTENT_CHECKSUMS = 2   # ZSK_IMAGE_CONTENT_CHECKSUMS
 IMAGE_ZSTD_FULL = 4           # ZSK_IMAGE_ZSTD_FULL
+IMAGE_ZSTD_WIDE = 8           # ZSK_IMAGE_ZSTD_WIDE
 
 
-def _image_flags(checksums: bool, content_checksums: bool, full: bool = False) -> int:
+def _image_flags(checksums: bool, content_checksums: bool, full: bool = False, wide: bool = False) -> int:
     return (IMAGE_CHECKSUMS if checksums else 0) | (IMAGE_CONTENT_CHECKSUMS if content_checksums else 0) | \
-        (IMAGE_ZSTD_FULL if full else 0)
+        (IMAGE_ZSTD_FULL if full else 0) | (IMAGE_ZSTD_WIDE if wide else 0)
 
 
 def zstd_image_bound(length: int, frame_size: int, checksums: bool = False) -> int:
@@ -1044,10 +1054,11 @@ def zstd_image_bound(length: int, frame_size: int, checksums: bool = False) -> i
 
 
 def zstd_build_image(src, frame_size: int, checksums: bool = False, content_checksums: bool = False,
-                     batch_bytes: int = 0, image=None, full: bool = False):
+                     batch_bytes: int = 0, image=None, full: bool = False, wide: bool = False):
     """zsk_zstd_build_image: the uint8 device tensor `src` as a complete
     seekable zstd file in device memory (synchronous), as lz4_build_image.
-    full=True: the frames in ZSK_ZSTD_FORMAT_FULL (ZSK_IMAGE_ZSTD_FULL).
+    full=True: the frames in ZSK_ZSTD_FORMAT_FULL (ZSK_IMAGE_ZSTD_FULL);
+    wide=True: in ZSK_ZSTD_FORMAT_FULL_WIDE (ZSK_IMAGE_ZSTD_WIDE).
     -> the file, a view of `image`."""
     import torch
     if not src.is_cuda or not src.is_contiguous() or src.dtype != torch.uint8:
@@ -1060,8 +1071,8 @@ def zstd_build_image(src, frame_size: int, checksums: bool = False, content_chec
     torch.cuda.current_stream(src.device).synchronize()   # the bytes must be complete
     err = C.create_string_buffer(ERRBUF)
     n = lib().zsk_zstd_build_image(src.data_ptr() if src.numel() else None, src.numel(), frame_size,
-                                   _image_flags(checksums, content_checksums, full), batch_bytes, image.data_ptr(),
-                                   image.numel(), err)
+                                   _image_flags(checksums, content_checksums, full, wide), batch_bytes,
+                                   image.data_ptr(), image.numel(), err)
     if n < 0:
         raise ZseekError(err.value.decode())
     return image[:n]

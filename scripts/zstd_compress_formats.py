@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""The two formats of the GPU zstd compressor side by side:
+"""The three formats of the GPU zstd compressor side by side:
 
   sizes   synth(4 MiB, seed 1), plain and with every byte's top bit flipped, at
-          64 KiB and 4 KiB frames: subset, full, libzstd level 1 and -1, liblz4
-  times   1 GiB of synth_buffer at 64 KiB and 1 MiB frames: HIP events around
-          one call, one warm-up, median of 5, subset and full alternated
-  --parent LIB   the subset call of this build against another build's
-          libzseek.so (the commit before), alternated, four runs each
+          64 KiB and 4 KiB frames: subset, full, wide, libzstd level 1 and -1,
+          liblz4; synth(8 MiB, seed 1) at 64 KiB and 1 MiB frames: full, wide
+  times   1 GiB of synth_buffer at 4 KiB, 64 KiB and 1 MiB frames: HIP events
+          around one call, one warm-up, median of 5, the three formats
+          alternated
+  --parent LIB   the subset and the full call of this build against another
+          build's libzseek.so (the commit before), alternated, four runs each
 
     python scripts/zstd_compress_formats.py [--gib 1] [--parent path/to/libzseek.so] [--out result.json]
 
@@ -46,6 +48,8 @@ def main() -> int:
     L = zs.lib()
     result = {"device": torch.cuda.get_device_name(0), "sizes": {}, "times": {}, "parent": {}}
 
+    FORMATS = (("subset", 0), ("full", 1), ("wide", zs.ZSTD_FORMAT_FULL_WIDE))
+
     def call(lib, fmt, d_desc, n, d_src, d_dst, d_cs, scratch):
         a = (d_desc.data_ptr(), n, d_src.data_ptr(), d_dst.data_ptr(), d_cs.data_ptr(), scratch.data_ptr(),
              scratch.numel(), torch.cuda.current_stream().cuda_stream)
@@ -57,7 +61,7 @@ def main() -> int:
         desc, total = zs.zstd_compress_layout([fs] * nf)
         return (torch.from_numpy(desc.view(np.uint8).copy()).to(dev), nf, torch.from_numpy(data).to(dev),
                 torch.empty(total, dtype=torch.uint8, device=dev), torch.zeros(nf, dtype=torch.int32, device=dev),
-                torch.empty(zs.zstd_compress_scratch_size(nf, data.size, full=True), dtype=torch.uint8, device=dev))
+                torch.empty(zs.zstd_compress_scratch_size(nf, data.size, wide=True), dtype=torch.uint8, device=dev))
 
     def timed(lib, fmt, st) -> float:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -75,7 +79,7 @@ def main() -> int:
             for fs in (65536, 4096):
                 st = setup(data, fs)
                 row = {}
-                for label, fmt in (("subset", 0), ("full", 1)):
+                for label, fmt in FORMATS:
                     call(L, fmt, *st)
                     torch.cuda.synchronize()
                     row[label] = int(st[4].sum().item())
@@ -90,17 +94,29 @@ def main() -> int:
                 print("sizes %-6s frame %6d: " % (name, fs) +
                       "  ".join("%s %d (%.4f)" % (k, v, v / data.size) for k, v in row.items()), flush=True)
 
+        data = Oracle().synth(8 << 20, 1)
+        for fs in (65536, 1 << 20):
+            st = setup(data, fs)
+            row = {}
+            for label, fmt in FORMATS[1:]:
+                call(L, fmt, *st)
+                torch.cuda.synchronize()
+                row[label] = int(st[4].sum().item())
+            result["sizes"]["synth8_%d" % fs] = row
+            print("sizes synth(8 MiB, 1) frame %7d: full %d  wide %d (%.4f of full)" %
+                  (fs, row["full"], row["wide"], row["wide"] / row["full"]), flush=True)
+
     # ---- times
     n = int(args.gib * (1 << 30)) & ~((1 << 20) - 1)
     big = zs.synth_buffer(n)
-    for fs in (65536, 1 << 20):
+    for fs in (4096, 65536, 1 << 20):
         st = setup(big, fs)
-        runs = {"subset": [], "full": []}
-        for label, fmt in (("subset", 0), ("full", 1)):
+        runs = {label: [] for label, _ in FORMATS}
+        for label, fmt in FORMATS:
             timed(L, fmt, st)                                   # warm-up
         size = {}
         for _ in range(5):
-            for label, fmt in (("subset", 0), ("full", 1)):
+            for label, fmt in FORMATS:
                 runs[label].append(timed(L, fmt, st))
                 size[label] = int(st[4].to(torch.int64).sum().item())
         row = {k: {"ms": v, "median_ms": statistics.median(v), "bytes": size[k]} for k, v in runs.items()}
@@ -112,15 +128,19 @@ def main() -> int:
             P = C.CDLL(args.parent)
             P.zsk_zstd_compress_frames.restype = C.c_int
             P.zsk_zstd_compress_frames.argtypes = L.zsk_zstd_compress_frames.argtypes
-            timed(P, None, st)
-            timed(L, None, st)
-            pr = {"parent": [], "this": []}
-            for _ in range(4):
-                pr["parent"].append(timed(P, None, st))
-                pr["this"].append(timed(L, None, st))
-            result["parent"][str(fs)] = pr
-            print("subset call, frame %7d: parent %s  this build %s" %
-                  (fs, ["%.2f" % x for x in pr["parent"]], ["%.2f" % x for x in pr["this"]]), flush=True)
+            P.zsk_zstd_compress_frames_ex.restype = C.c_int
+            P.zsk_zstd_compress_frames_ex.argtypes = L.zsk_zstd_compress_frames_ex.argtypes
+            result["parent"][str(fs)] = {}
+            for label, fmt in (("subset", None), ("full", 1)):
+                timed(P, fmt, st)
+                timed(L, fmt, st)
+                pr = {"parent": [], "this": []}
+                for _ in range(4):
+                    pr["parent"].append(timed(P, fmt, st))
+                    pr["this"].append(timed(L, fmt, st))
+                result["parent"][str(fs)][label] = pr
+                print("%s call, frame %7d: parent %s  this build %s" %
+                      (label, fs, ["%.2f" % x for x in pr["parent"]], ["%.2f" % x for x in pr["this"]]), flush=True)
         del st
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
