@@ -96,6 +96,16 @@ typedef struct {
  * @d_comp must stay readable up to the 4-byte boundary after the last
  * compressed byte.  Each frame writes only its own [d_off, d_off+d_size).
  * Returns 0 if the launch was queued, -1 otherwise.
+ *
+ * Scratch: the call has no reader to own scratch and takes a set from a pool
+ * of at most four per device, for the time the call itself runs on the host
+ * (not for the time its kernels run).  Sets are reused in stream order: the
+ * set the same stream used last is taken as it is, one whose work has
+ * completed by any stream, and otherwise @stream is made to wait
+ * (hipStreamWaitEvent) for the least recently used set's last call.  Any
+ * number of calls may be queued; with four calls of this entry point (or of
+ * zsk_lz4_decode_frames_ex) in progress on a device at once, in other threads,
+ * a fifth gets -1 with nothing queued and @d_status and @d_out untouched.
  */
 ZSEEK_EXPORT int zsk_lz4_decode_frames(const zsk_frame_desc_t *d_desc,
     uint32_t nframes, const void *d_comp, void *d_out, int32_t *d_status,
@@ -109,6 +119,12 @@ ZSEEK_EXPORT int zsk_lz4_decode_frames(const zsk_frame_desc_t *d_desc,
  * ZSTD_ErrorCode libzstd 1.4.9 reports for it.  The call synchronizes
  * @stream once, after the planning kernel (a frame's sequence count sizes its
  * scratch), and returns with the decode queued.  Returns 0 or -1.
+ *
+ * Scratch: pooled as zsk_lz4_decode_frames' (a pool of its own, shared with
+ * zsk_zstd_decode_frames_async): at most four sets per device, reused in
+ * stream order, held while the call runs on the host -- here that includes
+ * the wait for the planning kernel.  A fifth call in progress at once on a
+ * device gets -1 with nothing queued and nothing written.
  */
 ZSEEK_EXPORT int zsk_zstd_decode_frames(const zsk_frame_desc_t *d_desc,
     uint32_t nframes, const void *d_comp, void *d_out, int32_t *d_status,
@@ -147,7 +163,9 @@ ZSEEK_EXPORT int zsk_zstd_decode_frames(const zsk_frame_desc_t *d_desc,
  * with larger bounds (freeing device memory waits for the device) -- the wait
  * zsk_preadv_device_async lists as its (1).  The scratch comes from the pool
  * zsk_zstd_decode_frames uses (at most four sets per device, reused in stream
- * order).  -1 and nothing queued for: NULL @bounds; a stream that is capturing
+ * order: see zsk_lz4_decode_frames).  -1 and nothing queued for: a fifth call
+ * of the two entry points in progress at once on the device (four other
+ * threads inside theirs); NULL @bounds; a stream that is capturing
  * (pooled scratch sized per call: it must never end up in a graph); bounds no
  * device could hold (max_blocks >= 2^29); an allocation or launch failure.
  * nframes == 0 returns 0 and queues nothing.
@@ -173,7 +191,8 @@ ZSEEK_EXPORT const char *zsk_status_string(int32_t status);
  * SCAN and CHUNK the two-phase decoder with that parse kernel for every frame;
  * BLOCK the two-phase decoder's block route (one parse lane per LZ4 block of
  * each multi-block frame, the chunk parse for the rest) at any batch size.
- * Returns -1 for an unknown decoder.
+ * Returns -1 for an unknown decoder.  Scratch and its bound of four calls in
+ * progress per device: zsk_lz4_decode_frames' pool (WAVE uses no scratch).
  */
 #define ZSK_DECODER_AUTO 0
 #define ZSK_DECODER_WAVE 1
@@ -542,9 +561,13 @@ ZSEEK_EXPORT int zsk_reader_zstd_census(zseek_reader_t *reader, zsk_zstd_census_
  * overlap, and destinations must be disjoint.  Asynchronous on @stream (the
  * segments are read on the stream too: keep @d_seg alive until it has
  * passed).  Returns 0 if queued (nseg == 0: nothing to do, 0), -1 otherwise.
+ * The segments' prefix sum goes into pooled scratch (a pool of this entry
+ * point's own; see zsk_lz4_decode_frames): at most four sets per device,
+ * reused in stream order, held while the call runs on the host; a fifth call
+ * in progress at once on a device gets -1 with nothing queued.
  */
 typedef struct {
-    uint64_t src_off;  /* into d_src                                          */
+    uint64_t src_off;  /* into d_src                                        */
     uint64_t dst_off;  /* into d_dst                                          */
     uint32_t len;      /* bytes                                               */
     uint32_t frame;    /* index into d_status                                 */
@@ -935,6 +958,13 @@ ZSEEK_EXPORT zseek_reader_t *zsk_reader_open_device(const void *d_image, size_t 
  * the bound ("build image: buffer too small", checked before anything is
  * written) and a HIP failure.  Nothing at or past @d_image + @capacity is ever
  * written; bytes between the returned size and @capacity are unspecified.
+ *
+ * Concurrent calls: the scratch is a pool of at most four sets per device,
+ * one pool for this entry point and zsk_zstd_build_image, a set held from the
+ * call's start to its end and reused in stream order (see
+ * zsk_lz4_decode_frames).  A fifth call in progress at once on a device gets
+ * -1 + "build image: scratch allocation failed" with nothing queued and
+ * @d_image untouched.
  */
 #define ZSK_IMAGE_CHECKSUMS 1u
 ZSEEK_EXPORT size_t zsk_lz4_image_bound(size_t len, size_t frame_size, unsigned flags);
@@ -963,6 +993,8 @@ ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t f
  * The pooled scratch is zsk_lz4_build_image's with the zstd compressor's in
  * place of the LZ4 tables: 512 KiB per frame of a batch, at most 896 MiB;
  * with ZSK_IMAGE_ZSTD_WIDE 576 KiB per frame of a batch, at most 1,008 MiB.
+ * Its bound is zsk_lz4_build_image's too: four calls of the two entry points
+ * in progress at once per device, a fifth gets -1 with nothing queued.
  */
 #define ZSK_IMAGE_CONTENT_CHECKSUMS 2u
 #define ZSK_IMAGE_ZSTD_FULL 4u     /* zsk_zstd_build_image: frames in the full format */

@@ -3,12 +3,14 @@
 // to own scratch.  Internal.
 //
 // A set is reused in stream order: after a call's launches its event is
-// recorded on the caller's stream; the next call (any stream) takes a set
-// whose event has completed, or one last released on the same stream (stream
-// order covers it), or a new set while the device has fewer than kPoolSets,
-// or else the least recently released set after making its stream wait on
-// that event.  Nothing is keyed by stream, so streams a caller destroys leave
-// no entries behind, and a device never holds more than kPoolSets sets.
+// recorded on the caller's stream; the next call (any stream) takes, in this
+// order, a set last released on the same stream (stream order covers it), or
+// one whose event has completed, or a new set while the device has fewer than
+// kPoolSets, or else the least recently released set after making its stream
+// wait on that event.  With every set held by a call in progress there is
+// none: nullptr.  Nothing is keyed by stream, so streams a caller destroys
+// leave no entries behind, and a device never holds more than kPoolSets sets.
+// (tests/test_pool.py, tests/test_gpu_pool_streams.py)
 #ifndef ZSK_POOL_H
 #define ZSK_POOL_H
 
