@@ -58,6 +58,14 @@
  *                            subset (valid zstd, not libzstd's bytes), and a
  *                            seekable zstd file built from them in device
  *                            memory.
+ *   zsk_lz4_build_image_pieces, zsk_zstd_build_image_pieces — the two image
+ *                            builders queued on the caller's stream, their
+ *                            answer left in device memory; with a list of
+ *                            piece sizes in device memory, one frame per piece
+ *                            (a writer's loop of one zseek_write per record,
+ *                            compress.c:650-833, planned where the list is).
+ *                            zsk_lz4_pieces_bound, zsk_zstd_pieces_bound: their
+ *                            capacity, from the piece count alone.
  */
 #ifndef ZSEEK_HIP_H
 #define ZSEEK_HIP_H
@@ -1002,6 +1010,94 @@ ZSEEK_EXPORT ssize_t zsk_lz4_build_image(const void *d_src, size_t len, size_t f
 ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_size, unsigned flags);
 ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size,
     unsigned flags, size_t batch_bytes, void *d_image, size_t capacity,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * zsk_lz4_build_image / zsk_zstd_build_image queued on the caller's stream,
+ * optionally with one frame per PIECE of a list that is in device memory.
+ *
+ * Stream order: everything is queued on @stream (a hipStream_t of the image's
+ * device; NULL = HIP's null stream, as in zsk_preadv_device_async), after what
+ * the stream already holds and before what is queued later -- work already on
+ * the stream may have written @d_src and @d_sizes.  The call returns 0 once
+ * everything is queued and makes no host wait for its own work.  The one thing
+ * that can make it wait: growing the pooled scratch (the first call, or a call
+ * that needs more than any before: hipFree waits for the device; the scratch
+ * is the synchronous builders', sized by @max_piece as they size it by
+ * frame_size).
+ *
+ * @d_result: three int64_t of device memory, written when the stream reaches
+ * the end of the call's work: [0] the file's size, or ZSK_IMAGE_FAILED (a frame
+ * was refused by the compressor, or a HIP failure after something was queued)
+ * or ZSK_IMAGE_BAD_PIECES; [1] the frames in the table; [2] the source bytes
+ * consumed.  Whatever is queued behind the call -- a copy of the result, a
+ * kernel that reads the table -- sees all three and the image.
+ *
+ * @d_sizes != NULL, a build from pieces: piece i is d_sizes[i] bytes of @d_src
+ * right after piece i - 1, and becomes frame i; frame index = piece index.
+ * LZ4: the image is byte for byte the file of a host writer opened with
+ * {ZSEEK_LZ4, @level} and min_frame_size = 1,
+ * zsk_writer_set_checksums(@flags & ZSK_IMAGE_CHECKSUMS), one zseek_write per
+ * piece, zseek_writer_close: every frame a direct frame without a content-size
+ * field, pieces above 64 KiB as linked 64 KiB blocks.  zstd: frame i is the
+ * frame zsk_zstd_compress_frames_ex writes for the piece's bytes in the format
+ * the flags select (the subset, ZSK_IMAGE_ZSTD_FULL, ZSK_IMAGE_ZSTD_WIDE);
+ * ZSK_IMAGE_CONTENT_CHECKSUMS as in zsk_zstd_build_image.  npieces == 0 gives
+ * the empty table alone (17 bytes).
+ * The list is data, not trusted input.  It is invalid when some size is 0,
+ * some size exceeds @max_piece, or the sizes sum to more than @src_len:
+ * d_result[0] is then ZSK_IMAGE_BAD_PIECES, no byte outside
+ * d_src[0, src_len) is read and none outside d_image[0, capacity) written
+ * (bytes inside the capacity are unspecified, [1] and [2] too), and the next
+ * call builds normally.  A sum below @src_len is valid: the rest of the source
+ * is ignored, and [2] says how much was used.
+ *
+ * @d_sizes == NULL, the fixed-frame build: pieces of @max_piece bytes, the
+ * last one the rest of @src_len; @npieces must be ceil(src_len / max_piece)
+ * ("build image: invalid piece count").  The image is exactly
+ * zsk_lz4_build_image's / zsk_zstd_build_image's for frame_size = max_piece,
+ * LZ4's content-size header on a short tail included.
+ *
+ * Batches hold min(@batch_bytes / @max_piece, the synchronous builders' frame
+ * caps, @npieces) pieces (at least one; @batch_bytes 0: their defaults), in
+ * slots of the bound of @max_piece; a batch of a build from pieces costs one
+ * more one-workgroup kernel (the scan and check of its sizes).
+ *
+ * zsk_lz4_pieces_bound / zsk_zstd_pieces_bound(src_len, npieces, flags): the
+ * capacity the call asks for, computable on the host without the sizes: at
+ * least the sum of ZSK_*_COMPRESS_BOUND over ANY npieces sizes that sum to at
+ * most src_len, plus the table --
+ *   LZ4   src_len + 4 * (src_len >> 16) + 39 * npieces + 17 + (8 | 12) * npieces
+ *   zstd  src_len + 3 * (src_len >> 17) + 31 * npieces + 17 + (8 | 12) * npieces
+ * (csrc/image_pieces.h derives them).  On a fixed-frame list it exceeds
+ * zsk_*_image_bound by at most 19 (LZ4) or 18 (zstd) bytes per piece.
+ *
+ * -1 + errbuf with nothing queued and @d_image untouched: a capturing stream
+ * ("build image: stream is capturing" -- pooled scratch must never end up in a
+ * graph); NULL @d_result ("build image: NULL result"); @max_piece 0 or above
+ * the codec's cap of 4 MiB ("build image: invalid piece size"); level >= 3;
+ * more pieces than a seek table holds; no HIP device ("no HIP device
+ * available"); @d_image, @d_result, @d_sizes when not NULL and @d_src when
+ * src_len > 0 not device memory of one device ("build image: not device memory
+ * of one device"), or @d_sizes / @d_result not aligned to their words;
+ * @capacity below the bound ("build image: buffer too small"); a fifth call of
+ * the four builder entry points in progress at once on a device (one pool, see
+ * zsk_lz4_build_image).  A HIP failure after something was queued queues a fill
+ * of d_result[0..2] with -1 and returns -1.
+ * Left out: graph capture, zero-length pieces, sources in host memory, pieces
+ * on another device than the image.
+ */
+#define ZSK_IMAGE_FAILED     (-1)
+#define ZSK_IMAGE_BAD_PIECES (-2)
+ZSEEK_EXPORT size_t zsk_lz4_pieces_bound(size_t src_len, size_t npieces, unsigned flags);
+ZSEEK_EXPORT size_t zsk_zstd_pieces_bound(size_t src_len, size_t npieces, unsigned flags);
+ZSEEK_EXPORT int zsk_lz4_build_image_pieces(const void *d_src, size_t src_len,
+    const uint32_t *d_sizes, size_t npieces, size_t max_piece, int level, unsigned flags,
+    size_t batch_bytes, void *d_image, size_t capacity, int64_t *d_result, void *stream,
+    char errbuf[ZSEEK_ERRBUF_SIZE]);
+ZSEEK_EXPORT int zsk_zstd_build_image_pieces(const void *d_src, size_t src_len,
+    const uint32_t *d_sizes, size_t npieces, size_t max_piece, unsigned flags,
+    size_t batch_bytes, void *d_image, size_t capacity, int64_t *d_result, void *stream,
     char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 #ifdef __cplusplus

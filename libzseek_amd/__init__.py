@@ -15,4 +15,6 @@ from .zseek import (  # noqa: F401
     zstd_image_bound, zstd_build_image, ZSTD_FORMAT_SUBSET, ZSTD_FORMAT_FULL, IMAGE_ZSTD_FULL,
     ZSTD_FORMAT_FULL_WIDE, IMAGE_ZSTD_WIDE,
     zstd_bounds_default, zstd_decode_frames_async, ERR_SCRATCH,
+    lz4_pieces_bound, zstd_pieces_bound, lz4_build_image_pieces, zstd_build_image_pieces,
+    IMAGE_FAILED, IMAGE_BAD_PIECES,
 )

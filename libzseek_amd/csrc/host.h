@@ -22,6 +22,12 @@ namespace zsk {
 void set_error(char *errbuf, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void set_error_errno(char *errbuf, const char *msg, int errnum);
 
+// The stream-ordered calls reuse pinned staging that the host rewrites, and
+// pooled scratch sized per call: they must never end up in a graph.  true,
+// with the entry's refusal ("<entry>: stream is capturing") in errbuf, when q
+// is capturing.
+bool refuse_capturing(hipStream_t q, const char *entry, char *errbuf);
+
 // In-memory seek table as prefix sums (ref src/seek_table.c:36-47, 62-110).
 // SoA so a batch's descriptors are built with two subtractions per frame.
 struct SeekTable {

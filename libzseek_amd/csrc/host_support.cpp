@@ -42,6 +42,17 @@ void set_error_errno(char *errbuf, const char *msg, int errnum)
         set_error(errbuf, "%s: %s", msg, s);
 }
 
+bool refuse_capturing(hipStream_t q, const char *entry, char *errbuf)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(q, &cap);
+    (void)hipGetLastError();   // (no device: reported later, where one is needed)
+    if ((ce != hipSuccess || cap == hipStreamCaptureStatusNone) && ce != hipErrorStreamCaptureImplicit)
+        return false;
+    set_error(errbuf, "%s: stream is capturing", entry);
+    return true;
+}
+
 // ---------------------------------------------------------------------------
 // seek table (ref src/seek_table.c:15-23 constants, :62-176 parse)
 // ---------------------------------------------------------------------------

@@ -23,6 +23,15 @@
 // then image_table_kernel writes the seek table at the running offset, byte by
 // byte (the image has any alignment), and the file's size and the failure
 // flag come down in one 24-byte copy: the call's only synchronization.
+//
+// The stream-ordered builds (build_image_pieces: zsk_lz4_build_image_pieces,
+// zsk_zstd_build_image_pieces) queue the same batches on the caller's stream
+// and wait for nothing: image_table_kernel leaves the answer in the caller's
+// d_result.  With a piece list in device memory image_pieces_kernel takes
+// image_cdesc_kernel's place: one workgroup that scans the batch's sizes on top
+// of the running SOURCE offset, which joins the file offset in the chained
+// state, and validates them (image_pieces.h; a sticky flag in that state turns
+// the pieces after an invalid one into nothing).
 // Plain vector loads and stores only.
 
 #include <hip/hip_runtime.h>
@@ -33,6 +42,7 @@
 
 #include "block_scan.h"
 #include "host.h"
+#include "image_pieces.h"
 #include "pool.h"
 #include "zsk_internal.h"
 
@@ -47,6 +57,7 @@ constexpr size_t kBatchSmall = 256u << 20;   // frames of <= 64 KiB (writer.cpp 
 constexpr size_t kBatchLinked = 1u << 30;    // linked frames: a launch costs one frame's chain
 constexpr size_t kTableBytes = 65536;        // compressor scratch per frame
 constexpr size_t kMaxBatchFrames = 65536;
+constexpr size_t kStateWords = 4;            // the chained state (image_plan_kernel)
 
 __global__ __launch_bounds__(256) void image_desc_kernel(const uint64_t *__restrict__ coff,
                                                          const uint64_t *__restrict__ doff, uint64_t f0, uint32_t n,
@@ -85,8 +96,76 @@ __global__ __launch_bounds__(256) void image_cdesc_kernel(zsk_compress_desc_t *_
     desc[i] = o;
 }
 
-// state[0]: the running file offset; state[1]: some frame was refused
-// (c_size 0); state[2]: the file's size (image_table_kernel).
+// The batch's descriptors of a build from device-listed pieces (image_pieces.h
+// holds the rule): one workgroup, image_plan_kernel's shape.  A 64-bit
+// exclusive scan of the batch's sizes on top of the running source offset
+// (state[3]) gives piece i its offset; the first piece that is not valid there
+// is found with it, and from that piece on (from 0 when an earlier batch set
+// the flag) every piece is the refused one, which reads no source byte.  The
+// offset stops at the first invalid piece and the flag stays set.
+__global__ __launch_bounds__(kPlanT) void image_pieces_kernel(const uint32_t *__restrict__ sizes, uint32_t n,
+                                                              uint64_t max_piece, uint64_t src_len, uint64_t slot,
+                                                              uint32_t flags, uint64_t *state,
+                                                              zsk_compress_desc_t *__restrict__ desc)
+{
+    __shared__ uint64_t s_sum[kPlanT];
+    __shared__ uint32_t s_bad;
+    const uint32_t t = threadIdx.x;
+    const uint64_t fl = state[1], base = state[3];
+    const bool sticky = (fl & kStateBadPieces) != 0;
+    if (t == 0)
+        s_bad = sticky ? 0u : kNoBadPiece;
+    uint32_t a, b;
+    block_share<kPlanT>(n, t, &a, &b);
+    uint64_t sum = 0;
+    for (uint32_t i = a; i < b; i++)
+        sum += sizes[i];
+    // (the scan's first barrier also orders s_bad's start value and every
+    // thread's reads of the state before the writes below)
+    const uint64_t incl = block_scan_inclusive<kPlanT>(s_sum, t, sum);
+    const uint64_t first = base + (incl - sum);
+    // up to the list's first invalid piece the scanned offsets are the true
+    // ones; what follows it is never used
+    uint32_t bad = kNoBadPiece;
+    uint64_t off = first, bad_off = 0;
+    for (uint32_t i = a; i < b && bad == kNoBadPiece; i++) {
+        if (!piece_valid(sizes[i], off, max_piece, src_len)) {
+            bad = i;
+            bad_off = off;
+        }
+        off = piece_advance(off, sizes[i]);
+    }
+    if (bad != kNoBadPiece)
+        atomicMin(&s_bad, bad);
+    __syncthreads();
+    const uint32_t first_bad = s_bad;
+    off = first;
+    for (uint32_t i = a; i < b; i++) {
+        const PieceSpan p = piece_span(i, sizes[i], off, first_bad);
+        zsk_compress_desc_t o;
+        o.src_off = p.src_off;
+        o.dst_off = (uint64_t)i * slot;
+        o.src_size = p.size;
+        o.flags = flags;
+        desc[i] = o;
+        off = piece_advance(off, sizes[i]);
+    }
+    if (sticky)
+        return;
+    if (first_bad == kNoBadPiece) {
+        if (t == kPlanT - 1)
+            state[3] = base + incl;
+    } else if (bad == first_bad) {   // (one thread: shares are disjoint)
+        state[3] = bad_off;
+        state[1] = fl | kStateBadPieces;
+    }
+}
+
+// state[0]: the running file offset; state[1]: kStateRefused, some frame was
+// refused (c_size 0), and kStateBadPieces (image_pieces_kernel), under which
+// every frame packs as nothing and the offset stays; state[2]: the file's size
+// (image_table_kernel); state[3]: the running source offset of a build from
+// pieces.
 __global__ __launch_bounds__(kPlanT) void image_plan_kernel(const uint32_t *__restrict__ csize,
                                                             const zsk_compress_desc_t *__restrict__ cdesc,
                                                             const uint32_t *__restrict__ sums, uint32_t n,
@@ -96,14 +175,16 @@ __global__ __launch_bounds__(kPlanT) void image_plan_kernel(const uint32_t *__re
 {
     __shared__ uint64_t s_sum[kPlanT];
     const uint32_t t = threadIdx.x;
-    const uint64_t base = state[0];
+    const uint64_t base = state[0], fl = state[1];
+    const bool drop = (fl & kStateBadPieces) != 0;
     uint32_t a, b;
     block_share<kPlanT>(n, t, &a, &b);
     uint64_t sum = 0;
     bool refused = false;
     for (uint32_t i = a; i < b; i++) {
-        sum += csize[i];
-        refused |= csize[i] == 0;
+        const uint32_t c = drop ? 0u : csize[i];
+        sum += c;
+        refused |= c == 0 && !drop;
     }
     // (range_gather.hip's scan, block_scan.h; its first barrier also orders
     // every thread's read of state[0] before the write below)
@@ -113,35 +194,45 @@ __global__ __launch_bounds__(kPlanT) void image_plan_kernel(const uint32_t *__re
         cum[0] = 0;
     for (uint32_t i = a; i < b; i++) {
         const zsk_compress_desc_t d = cdesc[i];
+        const uint32_t c = drop ? 0u : csize[i];
         GatherSeg g;
         g.src_off = d.dst_off;
         g.dst_off = base + run;
-        g.len = csize[i];
+        g.len = c;
         g.frame = i;
         seg[i] = g;
-        run += csize[i];
+        run += c;
         cum[i + 1] = run;
         uint32_t *e = entries + (frame0 + i) * ew;
-        e[0] = csize[i];
+        e[0] = c;
         e[1] = d.src_size;
         if (ew == 3)
             e[2] = sums[i];
     }
     if (refused)
-        state[1] = 1;
+        state[1] = fl | kStateRefused;
     if (t == kPlanT - 1)
         state[0] = base + incl;
 }
 
 // The seek table at state[0] (ref seek_table.c:365-419): skippable header,
 // frames x {cSize, dSize[, checksum]}, the frame count, the descriptor byte,
-// the magic -- each thread one byte at a time.
+// the magic -- each thread one byte at a time.  With @result (the stream-ordered
+// builds) the call's answer is written here too: the file's size or the
+// failure, the frame count, and the source bytes consumed (state[3] for a
+// build from pieces, else @consumed); an invalid piece list writes no table.
 __global__ __launch_bounds__(256) void image_table_kernel(uint8_t *__restrict__ image, uint64_t *state,
                                                           const uint32_t *__restrict__ entries, uint32_t frames,
-                                                          uint32_t ew)
+                                                          uint32_t ew, int64_t *__restrict__ result, uint64_t consumed,
+                                                          uint32_t pieces)
 {
-    const uint64_t at = state[0];
-    const uint64_t body = 4ull * ew * frames, size = 8 + body + 9;
+    const uint64_t at = state[0], fl = result ? state[1] : 0;
+    const uint64_t body = 4ull * ew * frames, size = (fl & kStateBadPieces) ? 0 : 8 + body + 9;
+    if (result && blockIdx.x == 0 && threadIdx.x == 0) {
+        result[0] = (fl & kStateBadPieces) ? kImageBadPieces : (fl & kStateRefused) ? kImageFailed : (int64_t)(at + size);
+        result[1] = frames;
+        result[2] = (int64_t)(pieces ? state[3] : consumed);
+    }
     for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < size; j += (uint64_t)gridDim.x * 256) {
         uint32_t w, k;
         if (j < 8) {
@@ -171,7 +262,7 @@ struct ImageScratch {
     size_t frames_cap = 0;
     uint8_t *entries = nullptr;    // the whole file's seek-table entries (u32 words)
     size_t entries_cap = 0;
-    uint64_t *state = nullptr;     // device, 3 words
+    uint64_t *state = nullptr;     // device, kStateWords words
     uint64_t *h_state = nullptr;   // pinned
 };
 
@@ -254,6 +345,109 @@ using namespace zsk;
 
 namespace {
 
+// One pool for the four builder entry points.
+ScratchPool<ImageScratch> &image_pool()
+{
+    static ScratchPool<ImageScratch> pool;
+    return pool;
+}
+
+// How a build is cut into batches and what its frames carry.
+struct Layout {
+    uint64_t frames, entry, slot;
+    uint32_t per, ew, cflags, tail_flags;
+    bool in_frame, ck;
+};
+
+// @frame_size: the frame size, or the largest piece of a build from pieces.
+Layout layout(const Codec &codec, uint64_t frames, size_t frame_size, unsigned flags, size_t batch_bytes)
+{
+    Layout L;
+    L.frames = frames;
+    L.entry = (flags & ZSK_IMAGE_CHECKSUMS) ? 12 : 8;
+    if (batch_bytes == 0)
+        batch_bytes = !codec.zstd && frame_size > 65536 ? kBatchLinked : kBatchSmall;
+    // frames per batch: batch_bytes of input, and the compressor's scratch
+    // (64 KiB per frame) within batch_bytes too, as the writer's GPU mode
+    const uint64_t cap_frames = std::min<uint64_t>(kMaxBatchFrames, std::max<uint64_t>(16, batch_bytes / kTableBytes));
+    L.per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, batch_bytes / frame_size),
+                                         std::min<uint64_t>(cap_frames, std::max<uint64_t>(frames, 1)));
+    L.slot = codec.bound(frame_size);
+    L.ew = (uint32_t)(L.entry / 4);
+    // zstd frames that end with their content checksum take the seek table's word
+    L.in_frame = codec.zstd && (flags & ZSK_IMAGE_CONTENT_CHECKSUMS);
+    L.ck = L.ew == 3 || L.in_frame;
+    L.cflags = L.in_frame ? ZSK_COMPRESS_CONTENT_CHECKSUM : 0u;
+    L.tail_flags = codec.zstd ? 0u : ZSK_COMPRESS_CONTENT_SIZE;
+    return L;
+}
+
+// The set sized for the build (hipFree, when a buffer grows, waits for the device).
+bool size_scratch(ImageScratch *s, const Codec &codec, const Layout &L)
+{
+    // per batch frame: cdesc (24), seg (24), cum (8, one more), csize, sums (4 + 4)
+    const size_t per_frame = sizeof(zsk_compress_desc_t) + sizeof(GatherSeg) + 8 + 4 + 4;
+    bool ok = grow(&s->slots, &s->slots_cap, L.frames ? L.per * L.slot : 0) &&
+              grow(&s->tables, &s->tables_cap, L.frames ? codec.scratch(L.per) : 0) &&
+              grow(&s->frames, &s->frames_cap, L.frames ? L.per * per_frame + 64 : 0) &&
+              grow(&s->entries, &s->entries_cap, std::max<size_t>(L.frames * L.entry, 16));
+    if (ok && !s->state)
+        ok = hipMalloc((void **)&s->state, kStateWords * sizeof(uint64_t)) == hipSuccess &&
+             hipHostMalloc((void **)&s->h_state, 3 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+    if (!ok)
+        (void)hipGetLastError();
+    return ok;
+}
+
+// The whole build queued on @stream, no host wait: the state cleared, the
+// batches, the table.  @d_sizes: the piece list (frame_size is then the largest
+// piece), or NULL for frames of @frame_size.  @d_result: where the table kernel
+// leaves the answer, or NULL (the synchronous builders read the state).
+bool queue_image(const Codec &codec, const Layout &L, ImageScratch *s, const uint8_t *src, uint64_t len,
+                 uint64_t frame_size, const uint32_t *d_sizes, int level, uint8_t *image, int64_t *d_result,
+                 hipStream_t stream)
+{
+    const uint32_t per = L.per;
+    // (8-byte members first: cum, cdesc, seg; then the words)
+    uint64_t *const d_cum = reinterpret_cast<uint64_t *>(s->frames);
+    zsk_compress_desc_t *const d_cdesc = reinterpret_cast<zsk_compress_desc_t *>(d_cum + per + 1);
+    GatherSeg *const d_seg = reinterpret_cast<GatherSeg *>(d_cdesc + per);
+    uint32_t *const d_csize = reinterpret_cast<uint32_t *>(d_seg + per);
+    uint32_t *const d_sums = d_csize + per;
+    uint32_t *const d_entries = reinterpret_cast<uint32_t *>(s->entries);
+
+    bool ok = hipMemsetAsync(s->state, 0, kStateWords * sizeof(uint64_t), stream) == hipSuccess;
+    for (uint64_t f = 0; ok && f < L.frames; f += per) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(per, L.frames - f);
+        if (d_sizes)
+            hipLaunchKernelGGL(image_pieces_kernel, dim3(1), dim3(kPlanT), 0, stream, d_sizes + f, n, frame_size, len,
+                               L.slot, L.cflags, s->state, d_cdesc);
+        else
+            hipLaunchKernelGGL(image_cdesc_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_cdesc, n,
+                               f * frame_size, frame_size, len, L.slot, L.cflags, L.tail_flags);
+        ok = hipGetLastError() == hipSuccess &&
+             (!L.ck || launch_src_checksums(d_cdesc, n, src, d_sums, stream) == 0) &&
+             (codec.zstd ? launch_zstd_compress(d_cdesc, n, src, s->slots, d_csize, s->tables, s->tables_cap,
+                                                L.in_frame ? d_sums : nullptr, stream, codec.format)
+                         : zsk_lz4_compress_frames(d_cdesc, n, src, s->slots, d_csize, level, s->tables, stream)) == 0;
+        if (!ok)
+            break;
+        hipLaunchKernelGGL(image_plan_kernel, dim3(1), dim3(kPlanT), 0, stream, d_csize, d_cdesc, d_sums, n, f, L.ew,
+                           s->state, d_seg, d_cum, d_entries);
+        // (the gather reads the bytes' total from d_cum; the bound only sizes its grid)
+        ok = hipGetLastError() == hipSuccess &&
+             launch_range_gather(d_seg, d_cum, n, (uint64_t)n * L.slot, s->slots, image, nullptr, stream) == 0;
+    }
+    if (ok) {
+        const uint64_t bytes = 8 + L.entry * L.frames + 9;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((bytes + 255) / 256, 2048);
+        hipLaunchKernelGGL(image_table_kernel, dim3(grid), dim3(256), 0, stream, image, s->state, d_entries,
+                           (uint32_t)L.frames, L.ew, d_result, len, d_sizes ? 1u : 0u);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    return ok;
+}
+
 ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t frame_size, int level, unsigned flags,
                     size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
 {
@@ -285,20 +479,7 @@ ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t fr
         set_error(errbuf, "build image: buffer too small");
         return -1;
     }
-    if (batch_bytes == 0)
-        batch_bytes = !codec.zstd && frame_size > 65536 ? kBatchLinked : kBatchSmall;
-    // frames per batch: batch_bytes of input, and the compressor's scratch
-    // (64 KiB per frame) within batch_bytes too, as the writer's GPU mode
-    const uint64_t cap_frames = std::min<uint64_t>(kMaxBatchFrames, std::max<uint64_t>(16, batch_bytes / kTableBytes));
-    const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, batch_bytes / frame_size),
-                                                      std::min<uint64_t>(cap_frames, std::max<uint64_t>(g.frames, 1)));
-    const uint64_t slot = codec.bound(frame_size);
-    const uint32_t ew = (uint32_t)(g.entry / 4);
-    // zstd frames that end with their content checksum take the seek table's word
-    const bool in_frame = codec.zstd && (flags & ZSK_IMAGE_CONTENT_CHECKSUMS);
-    const bool ck = ew == 3 || in_frame;
-    const uint32_t cflags = in_frame ? ZSK_COMPRESS_CONTENT_CHECKSUM : 0u;
-    const uint32_t tail_flags = codec.zstd ? 0u : ZSK_COMPRESS_CONTENT_SIZE;
+    const Layout L = layout(codec, g.frames, frame_size, flags, batch_bytes);
 
     DeviceGuard keep;
     hipStream_t stream = nullptr;
@@ -307,64 +488,22 @@ ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t fr
         set_error(errbuf, "build image: create HIP stream failed");
         return -1;
     }
-    static ScratchPool<ImageScratch> pool;
+    ScratchPool<ImageScratch> &pool = image_pool();
     ImageScratch *s = pool.acquire(stream);
     if (!s) {
         hip_stream_put(stream);
         set_error(errbuf, "build image: scratch allocation failed");
         return -1;
     }
-    // per batch frame: cdesc (24), seg (24), cum (8, one more), csize, sums (4 + 4)
-    const size_t per_frame = sizeof(zsk_compress_desc_t) + sizeof(GatherSeg) + 8 + 4 + 4;
-    bool ok = grow(&s->slots, &s->slots_cap, g.frames ? per * slot : 0) &&
-              grow(&s->tables, &s->tables_cap, g.frames ? codec.scratch(per) : 0) &&
-              grow(&s->frames, &s->frames_cap, g.frames ? per * per_frame + 64 : 0) &&
-              grow(&s->entries, &s->entries_cap, std::max<size_t>(g.frames * g.entry, 16));
-    if (ok && !s->state)
-        ok = hipMalloc((void **)&s->state, 3 * sizeof(uint64_t)) == hipSuccess &&
-             hipHostMalloc((void **)&s->h_state, 3 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
+    if (!size_scratch(s, codec, L)) {
         pool.release(s, stream);
         hip_stream_put(stream);
         set_error(errbuf, "build image: scratch allocation failed");
         return -1;
     }
-    // (8-byte members first: cum, cdesc, seg; then the words)
-    uint64_t *const d_cum = reinterpret_cast<uint64_t *>(s->frames);
-    zsk_compress_desc_t *const d_cdesc = reinterpret_cast<zsk_compress_desc_t *>(d_cum + per + 1);
-    GatherSeg *const d_seg = reinterpret_cast<GatherSeg *>(d_cdesc + per);
-    uint32_t *const d_csize = reinterpret_cast<uint32_t *>(d_seg + per);
-    uint32_t *const d_sums = d_csize + per;
-    uint32_t *const d_entries = reinterpret_cast<uint32_t *>(s->entries);
-    const uint8_t *const src = static_cast<const uint8_t *>(d_src);
-    uint8_t *const image = static_cast<uint8_t *>(d_image);
-
-    ok = hipMemsetAsync(s->state, 0, 3 * sizeof(uint64_t), stream) == hipSuccess;
-    for (uint64_t f = 0; ok && f < g.frames; f += per) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(per, g.frames - f);
-        hipLaunchKernelGGL(image_cdesc_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_cdesc, n,
-                           f * (uint64_t)frame_size, (uint64_t)frame_size, (uint64_t)len, slot, cflags, tail_flags);
-        ok = hipGetLastError() == hipSuccess && (!ck || launch_src_checksums(d_cdesc, n, src, d_sums, stream) == 0) &&
-             (codec.zstd ? launch_zstd_compress(d_cdesc, n, src, s->slots, d_csize, s->tables, s->tables_cap,
-                                                in_frame ? d_sums : nullptr, stream, codec.format)
-                         : zsk_lz4_compress_frames(d_cdesc, n, src, s->slots, d_csize, level, s->tables, stream)) == 0;
-        if (!ok)
-            break;
-        hipLaunchKernelGGL(image_plan_kernel, dim3(1), dim3(kPlanT), 0, stream, d_csize, d_cdesc, d_sums, n, f, ew,
-                           s->state, d_seg, d_cum, d_entries);
-        // (the gather reads the bytes' total from d_cum; the bound only sizes its grid)
-        ok = hipGetLastError() == hipSuccess &&
-             launch_range_gather(d_seg, d_cum, n, (uint64_t)n * slot, s->slots, image, nullptr, stream) == 0;
-    }
-    if (ok) {
-        const uint64_t bytes = 8 + g.entry * g.frames + 9;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((bytes + 255) / 256, 2048);
-        hipLaunchKernelGGL(image_table_kernel, dim3(grid), dim3(256), 0, stream, image, s->state, d_entries,
-                           (uint32_t)g.frames, ew);
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(s->h_state, s->state, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
-    }
+    const bool ok = queue_image(codec, L, s, static_cast<const uint8_t *>(d_src), len, frame_size, nullptr, level,
+                                static_cast<uint8_t *>(d_image), nullptr, stream) &&
+                    hipMemcpyAsync(s->h_state, s->state, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream) == hipSuccess;
     // the call's one synchronization (also drains what a failed step queued)
     const hipError_t e = hipStreamSynchronize(stream);
     const uint64_t size = ok && e == hipSuccess ? s->h_state[2] : 0;
@@ -381,6 +520,99 @@ ssize_t build_image(const Codec &codec, const void *d_src, size_t len, size_t fr
         return -1;
     }
     return (ssize_t)size;
+}
+
+// zsk_lz4_build_image_pieces / zsk_zstd_build_image_pieces: the same build
+// queued on the caller's stream, the answer left in d_result by the table
+// kernel.  Every refusal below comes before anything is queued.
+int build_image_pieces(const Codec &codec, const void *d_src, size_t src_len, const uint32_t *d_sizes, size_t npieces,
+                       size_t max_piece, int level, unsigned flags, size_t batch_bytes, void *d_image,
+                       size_t capacity, int64_t *d_result, void *stream, char *errbuf)
+{
+    hipStream_t const q = static_cast<hipStream_t>(stream);
+    if (refuse_capturing(q, "build image", errbuf))
+        return -1;
+    if (!d_result) {
+        set_error(errbuf, "build image: NULL result");
+        return -1;
+    }
+    if (max_piece == 0 || max_piece > codec.max_frame) {
+        set_error(errbuf, "build image: invalid piece size");
+        return -1;
+    }
+    if (level >= 3) {
+        set_error(errbuf, "build image: HC levels are not supported");
+        return -1;
+    }
+    if (npieces > kMaxFrames) {
+        set_error(errbuf, "build image: Frame index is too large");
+        return -1;
+    }
+    if (!d_sizes && npieces != src_len / max_piece + (src_len % max_piece ? 1 : 0)) {
+        set_error(errbuf, "build image: invalid piece count");
+        return -1;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+        (void)hipGetLastError();
+        set_error(errbuf, "no HIP device available");
+        return -1;
+    }
+    int dev = -1, other = -1;
+    if (!device_pointer(d_image, &dev) || !device_pointer(d_result, &other) || other != dev ||
+        (src_len && (!device_pointer(d_src, &other) || other != dev)) ||
+        (d_sizes && (!device_pointer(d_sizes, &other) || other != dev))) {
+        set_error(errbuf, "build image: not device memory of one device");
+        return -1;
+    }
+    if ((reinterpret_cast<uintptr_t>(d_result) & 7) || (reinterpret_cast<uintptr_t>(d_sizes) & 3)) {
+        set_error(errbuf, "build image: misaligned sizes or result");
+        return -1;
+    }
+    const bool sums = (flags & ZSK_IMAGE_CHECKSUMS) != 0;
+    if (capacity < (codec.zstd ? zstd_pieces_bound(src_len, npieces, sums) : lz4_pieces_bound(src_len, npieces, sums))) {
+        set_error(errbuf, "build image: buffer too small");
+        return -1;
+    }
+    const Layout L = layout(codec, npieces, max_piece, flags, batch_bytes);
+
+    DeviceGuard keep;
+    if (hipSetDevice(dev) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(errbuf, "build image: set HIP device failed");
+        return -1;
+    }
+    ScratchPool<ImageScratch> &pool = image_pool();
+    ImageScratch *s = pool.acquire(q);
+    if (!s) {
+        set_error(errbuf, "build image: scratch allocation failed");
+        return -1;
+    }
+    if (!size_scratch(s, codec, L)) {
+        pool.release(s, q);
+        set_error(errbuf, "build image: scratch allocation failed");
+        return -1;
+    }
+    // (an empty source has no byte to read: every listed piece is then invalid,
+    // and the launchers only want a pointer that is not NULL)
+    uint8_t *const image = static_cast<uint8_t *>(d_image);
+    const uint8_t *const src = src_len ? static_cast<const uint8_t *>(d_src) : image;
+    const bool ok = queue_image(codec, L, s, src, src_len, max_piece, d_sizes, level, image, d_result, q);
+    if (!ok) {
+        // all ones in the three words: ZSK_IMAGE_FAILED, behind whatever was queued
+        (void)hipGetLastError();
+        (void)hipMemsetAsync(d_result, 0xFF, 3 * sizeof(int64_t), q);
+        (void)hipGetLastError();
+        set_error(errbuf, "build image: GPU launch failed");
+    }
+    pool.release(s, q);
+    return ok ? 0 : -1;
+}
+
+const Codec &zstd_codec(unsigned flags)
+{
+    // (the wide search implies the full format)
+    return (flags & ZSK_IMAGE_ZSTD_WIDE) ? kZstdWide : (flags & ZSK_IMAGE_ZSTD_FULL) ? kZstdFull : kZstd;
 }
 
 }   // namespace
@@ -407,7 +639,33 @@ extern "C" ZSEEK_EXPORT size_t zsk_zstd_image_bound(size_t len, size_t frame_siz
 extern "C" ZSEEK_EXPORT ssize_t zsk_zstd_build_image(const void *d_src, size_t len, size_t frame_size, unsigned flags,
                                                      size_t batch_bytes, void *d_image, size_t capacity, char *errbuf)
 {
-    // (the wide search implies the full format)
-    const Codec &codec = (flags & ZSK_IMAGE_ZSTD_WIDE) ? kZstdWide : (flags & ZSK_IMAGE_ZSTD_FULL) ? kZstdFull : kZstd;
-    return build_image(codec, d_src, len, frame_size, 0, flags, batch_bytes, d_image, capacity, errbuf);
+    return build_image(zstd_codec(flags), d_src, len, frame_size, 0, flags, batch_bytes, d_image, capacity, errbuf);
+}
+
+extern "C" ZSEEK_EXPORT size_t zsk_lz4_pieces_bound(size_t src_len, size_t npieces, unsigned flags)
+{
+    return (size_t)lz4_pieces_bound(src_len, npieces, (flags & ZSK_IMAGE_CHECKSUMS) != 0);
+}
+
+extern "C" ZSEEK_EXPORT size_t zsk_zstd_pieces_bound(size_t src_len, size_t npieces, unsigned flags)
+{
+    return (size_t)zstd_pieces_bound(src_len, npieces, (flags & ZSK_IMAGE_CHECKSUMS) != 0);
+}
+
+extern "C" ZSEEK_EXPORT int zsk_lz4_build_image_pieces(const void *d_src, size_t src_len, const uint32_t *d_sizes,
+                                                       size_t npieces, size_t max_piece, int level, unsigned flags,
+                                                       size_t batch_bytes, void *d_image, size_t capacity,
+                                                       int64_t *d_result, void *stream, char *errbuf)
+{
+    return build_image_pieces(kLz4, d_src, src_len, d_sizes, npieces, max_piece, level, flags, batch_bytes, d_image,
+                              capacity, d_result, stream, errbuf);
+}
+
+extern "C" ZSEEK_EXPORT int zsk_zstd_build_image_pieces(const void *d_src, size_t src_len, const uint32_t *d_sizes,
+                                                        size_t npieces, size_t max_piece, unsigned flags,
+                                                        size_t batch_bytes, void *d_image, size_t capacity,
+                                                        int64_t *d_result, void *stream, char *errbuf)
+{
+    return build_image_pieces(zstd_codec(flags), d_src, src_len, d_sizes, npieces, max_piece, 0, flags, batch_bytes,
+                              d_image, capacity, d_result, stream, errbuf);
 }

@@ -424,20 +424,6 @@ void grow_idle_for_async(VecJob &V, DeviceCtx &g, size_t table_up, size_t table_
             (void)c.reserve(table_up, table_total, err);
 }
 
-// The stream-ordered calls reuse pinned staging that the host rewrites, and
-// scratch sized per call: they must never end up in a graph.  true, with the
-// entry's refusal in errbuf, when q is capturing.
-bool refuse_capturing(hipStream_t q, const char *entry, char *errbuf)
-{
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(q, &cap);
-    (void)hipGetLastError();   // (no device: reported later, where one is needed)
-    if ((ce != hipSuccess || cap == hipStreamCaptureStatusNone) && ce != hipErrorStreamCaptureImplicit)
-        return false;
-    set_error(errbuf, "%s: stream is capturing", entry);
-    return true;
-}
-
 // A stream-ordered call with no ranges: d_result[0] = 0 alone.
 ssize_t answer_no_ranges(int64_t *d_result, hipStream_t q, char *errbuf)
 {

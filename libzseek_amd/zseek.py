@@ -136,6 +136,7 @@ EXPORTED = [
     "zsk_zstd_compress_scratch_size_ex", "zsk_zstd_compress_frames_ex",
     "zsk_zstd_bounds_default", "zsk_zstd_decode_frames_async", "zsk_reader_set_zstd_async",
     "zsk_reader_zstd_census",
+    "zsk_lz4_pieces_bound", "zsk_zstd_pieces_bound", "zsk_lz4_build_image_pieces", "zsk_zstd_build_image_pieces",
 ]
 
 _lib = None
@@ -270,6 +271,17 @@ def lib() -> C.CDLL:
     L.zsk_zstd_build_image.restype = C.c_ssize_t
     L.zsk_zstd_build_image.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t,
                                        C.c_void_p, C.c_size_t, C.c_char_p]
+    for fn in (L.zsk_lz4_pieces_bound, L.zsk_zstd_pieces_bound):
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_size_t, C.c_size_t, C.c_uint]
+    L.zsk_lz4_build_image_pieces.restype = C.c_int
+    L.zsk_lz4_build_image_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                             C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_char_p]
+    L.zsk_zstd_build_image_pieces.restype = C.c_int
+    L.zsk_zstd_build_image_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_char_p]
     _lib = L
     return L
 
@@ -1076,6 +1088,68 @@ def zstd_build_image(src, frame_size: int, checksums: bool = False, content_chec
     if n < 0:
         raise ZseekError(err.value.decode())
     return image[:n]
+
+
+IMAGE_FAILED = -1       # ZSK_IMAGE_FAILED
+IMAGE_BAD_PIECES = -2   # ZSK_IMAGE_BAD_PIECES
+
+
+def lz4_pieces_bound(src_len: int, npieces: int, checksums: bool = False) -> int:
+    """zsk_lz4_pieces_bound: the capacity zsk_lz4_build_image_pieces asks for."""
+    return int(lib().zsk_lz4_pieces_bound(src_len, npieces, IMAGE_CHECKSUMS if checksums else 0))
+
+
+def zstd_pieces_bound(src_len: int, npieces: int, checksums: bool = False) -> int:
+    """zsk_zstd_pieces_bound: the capacity zsk_zstd_build_image_pieces asks for."""
+    return int(lib().zsk_zstd_pieces_bound(src_len, npieces, IMAGE_CHECKSUMS if checksums else 0))
+
+
+def _pieces_args(src, sizes, max_piece, image, result, stream, src_len, npieces, capacity):
+    """The pointer and count arguments of the *_build_image_pieces calls from
+    device tensors or raw device pointers (ints; the counts are then needed)."""
+    def ptr(x):
+        return x if x is None or isinstance(x, int) else x.data_ptr()
+    if src_len is None:
+        src_len = src.numel()
+    if npieces is None:
+        npieces = -(-src_len // max_piece) if sizes is None else sizes.numel()
+    if capacity is None:
+        capacity = image.numel()
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return ptr(src) if src_len else None, src_len, ptr(sizes), npieces, ptr(image), capacity, ptr(result), stream
+
+
+def lz4_build_image_pieces(src, sizes, max_piece: int, image, result, level: int = 0, checksums: bool = False,
+                           batch_bytes: int = 0, stream: int | None = None, src_len: int | None = None,
+                           npieces: int | None = None, capacity: int | None = None) -> None:
+    """zsk_lz4_build_image_pieces: queue, on `stream` (default: torch's
+    current stream), the build of a seekable LZ4 file in `image` with one frame
+    per piece of `sizes` (a device tensor of 32-bit sizes, or None for frames
+    of max_piece bytes) from `src`; the answer lands in `result`, three int64
+    of device memory (the file's size or IMAGE_FAILED / IMAGE_BAD_PIECES, the
+    frames, the source bytes used).  No host wait: read `result` in stream
+    order.  src / sizes / image / result: device tensors, or raw device
+    pointers with src_len / npieces / capacity given."""
+    s, n, z, k, im, cap, res, q = _pieces_args(src, sizes, max_piece, image, result, stream, src_len, npieces, capacity)
+    err = C.create_string_buffer(ERRBUF)
+    if lib().zsk_lz4_build_image_pieces(s, n, z, k, max_piece, level, IMAGE_CHECKSUMS if checksums else 0,
+                                        batch_bytes, im, cap, res, q, err) != 0:
+        raise ZseekError(err.value.decode())
+
+
+def zstd_build_image_pieces(src, sizes, max_piece: int, image, result, checksums: bool = False,
+                            content_checksums: bool = False, full: bool = False, wide: bool = False,
+                            batch_bytes: int = 0, stream: int | None = None, src_len: int | None = None,
+                            npieces: int | None = None, capacity: int | None = None) -> None:
+    """zsk_zstd_build_image_pieces, as lz4_build_image_pieces; the flags are
+    zstd_build_image's."""
+    s, n, z, k, im, cap, res, q = _pieces_args(src, sizes, max_piece, image, result, stream, src_len, npieces, capacity)
+    err = C.create_string_buffer(ERRBUF)
+    if lib().zsk_zstd_build_image_pieces(s, n, z, k, max_piece, _image_flags(checksums, content_checksums, full, wide),
+                                         batch_bytes, im, cap, res, q, err) != 0:
+        raise ZseekError(err.value.decode())
 
 
 def with_frame_checksums(image, checksums) -> np.ndarray:
