@@ -65,7 +65,15 @@ def sequences(img, c_off, fr):
 
 
 def batches(fr, outb, ns):
-    """seq_exec's cut: up to ns sequences whose output fits outb bytes"""
+    """seq_exec's cut over item lanes: up to ns lanes whose output fits outb
+    bytes.  fr: (literal length, match length, offset[, first half]) per lane;
+    a lane with a true fourth field is the first half of an extended pair (its
+    second half, the next lane, has no length) and the pair is never split: a
+    full batch that would end on a first half leaves it to the next batch, and
+    a lone first lane too long for outb (the nb == 0 step) takes its second
+    half with it.  Yields (first lane, end lane, output position)."""
+    def first_half(x):
+        return len(x) > 3 and x[3]
     i = pos = 0
     while i < len(fr):
         j = i
@@ -75,9 +83,27 @@ def batches(fr, outb, ns):
             j += 1
         if j == i:
             j = i + 1
+        if first_half(fr[j - 1]):
+            j += 1 if j - i < ns else -1
         yield i, j, pos
-        pos += sum(a + b for a, b, _ in fr[i:j])
+        pos += sum(x[0] + x[1] for x in fr[i:j])
         i = j
+
+
+def exact_rounds(ms):
+    """the readiness search of seq_exec: ms = a batch's pending matches in lane
+    order as (mb, me, msrc, need); match a waits while a lower pending match b
+    has me_b > msrc_a and mb_b < need_a.  -> the round (1, 2, ...) each is
+    copied in"""
+    rnd, todo, r = [0] * len(ms), list(range(len(ms))), 0
+    while todo:
+        r += 1
+        ready = [a for a in todo if not any(b < a and ms[b][1] > ms[a][2] and ms[b][0] < ms[a][3]
+                                            for b in todo)]
+        for a in ready:
+            rnd[a] = r
+        todo = [a for a in todo if a not in ready]
+    return rnd
 
 
 def rounds(S, outb, ns):
@@ -93,13 +119,7 @@ def rounds(S, outb, ns):
                         ms.append((mb, mb + M, mb - O, need))
                 p = mb + M
             pend += len(ms)
-            todo, r = list(range(len(ms))), 0
-            while todo:
-                ready = [a for a in todo if not any(b < a and ms[b][1] > ms[a][2] and ms[b][0] < ms[a][3]
-                                                    for b in todo)]
-                todo = [a for a in todo if a not in ready]
-                r += 1
-            rx += r
+            rx += max(exact_rounds(ms), default=0)
             todo, r = list(range(len(ms))), 0
             while todo:
                 f = ms[todo[0]][0]
