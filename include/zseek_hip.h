@@ -33,6 +33,10 @@
  *                            too, planned by kernels from the seek table a
  *                            device-image reader keeps resident (a zstd
  *                            reader: after zsk_reader_zstd_census).
+ *   zsk_read_frames_indirect — a caller's loop of zseek_pread calls over
+ *                            whole frames picked by index, the indices in
+ *                            device memory, each frame decoded in place into
+ *                            a packed or padded-rows batch.
  *   zsk_reader_zstd_census — no reference function: the largest scratch need
  *                            of any one entry of a zstd file in device
  *                            memory, from one walk over the whole file; what
@@ -515,6 +519,125 @@ ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *reader,
     void *d_buf, size_t buf_size,
     const zsk_range_t *d_ranges, size_t nranges, size_t max_frames,
     int64_t *d_result, void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * Whole frames by INDEX, the indices in DEVICE memory, each frame decoded in
+ * place: the read side of zsk_lz4_build_image_pieces / zsk_zstd_build_image_
+ * pieces, where the frame index is the record index.  On a reader over a
+ * device image (zsk_reader_open_device; LZ4, or zstd after
+ * zsk_reader_zstd_census, below).  Slot i of the list (i < @nidx) asks for
+ * seek-table frame d_idx[i], whole.  Kernels on @stream turn the list into
+ * frame descriptors from the seek table the reader keeps on the device --
+ * sizes, a scan of them, destinations -- and the decode kernels write every
+ * frame straight into @d_buf at its slot's offset: no staging, no gather, no
+ * seek-table download, no max_frames to guess, and each decoded byte is
+ * written once.  Nothing but the call's arguments goes host -> device, no
+ * pinned staging is rewritten, and the host waits only as listed below.
+ *
+ * @d_idx: @nidx int64_t in device memory, read on @stream: work queued on
+ * @stream before the call may have written them; they must stay valid and
+ * unchanged until the stream has passed the call's work; they are never
+ * written.  @d_result: nidx + 1 int64_t in device memory.  @d_buf[0,
+ * buf_size): the destination, 16-byte aligned.  The call returns 0 once
+ * everything is queued.
+ *
+ * Layout.  @stride == 0, packed: slot i goes to d_buf + d_offsets[i], where
+ * d_offsets[i] is the sum of the decoded sizes of the valid slots before i (a
+ * slot whose index is invalid counts 0) and d_offsets[nidx] the total.  The
+ * total is written whatever @buf_size is, so a caller whose buffer was too
+ * small learns the size it needs.  @d_offsets: nidx + 1 uint64_t in device
+ * memory, required.  @stride > 0, padded rows: slot i goes to d_buf + i *
+ * stride; @d_offsets may be NULL, and when given receives i * stride, and nidx
+ * * stride in its last entry.
+ *
+ * When the stream reaches the end of the call's work, d_result[i] is
+ *   - the frame's decoded size when the frame was decoded and its status is
+ *     ZSK_OK (with zsk_reader_set_verify_checksums on: and its seek-table
+ *     checksum matched; the words come from the resident table);
+ *   - 0 for a frame of decoded size 0: delivered, nothing decoded, wherever
+ *     its offset lies;
+ *   - -1 when the index is no frame of the file (negative, or >= frames), when
+ *     the slot's region [off, off + size) is not inside [0, buf_size), when
+ *     in rows mode size > stride (a frame is never truncated to its row), or
+ *     when the frame failed;
+ * and d_result[nidx] is the number of delivered slots (those with d_result[i]
+ * >= 0).
+ *
+ * The list is data, not trusted input: a garbage list gives -1 slots; it can
+ * never make the call write outside d_buf[0, buf_size).  Nothing outside the
+ * slots' own regions is ever written -- in rows mode the bytes between a
+ * frame's end and the next row are untouched -- and the bytes of a failed
+ * slot's region are unspecified.
+ *
+ * Duplicates.  A repeated index is decoded once per occurrence, each into its
+ * own region: two slots, two decodes.  Removing duplicates would need the
+ * touched-frame bitmap, a staging buffer and a copy per slot, which is what
+ * this call exists to avoid; a caller whose lists repeat heavily uses
+ * zsk_preadv_device_indirect.
+ *
+ * Span.  When the compressed bytes from the lowest touched frame's start to
+ * the highest one's end (over the slots with a valid index and a non-empty
+ * frame, fitting or not) are 2 GiB (less 256 bytes) or more -- the parse
+ * kernels address a wave's frames through one 32-bit buffer resource --
+ * nothing is decoded: @d_buf is untouched, every d_result[i] is -1 and
+ * d_result[nidx] is ZSK_PLAN_SPAN.  d_offsets is written as always.  The check
+ * is made on the device per call, as in zsk_preadv_device_indirect.
+ *
+ * The call is ONE batch.  Its parse scratch and, for zstd, its literal scratch
+ * are bounded by nidx x (stride ? stride : the file's largest frame dSize); it
+ * is refused up front when that exceeds the reader's batch size
+ * (zsk_reader_set_batch_bytes): -1, "frame-list read: the list exceeds the
+ * batch size" (and when it reaches 4 GiB: "... exceeds 4 GiB").  A longer
+ * list is the caller's loop.
+ *
+ * Neither consults nor fills the frame cache; holds the reader's exclusive
+ * lock for the enqueue only.  Counters: `batches` advances by 1 at enqueue;
+ * frames_decoded and bytes_decoded do NOT advance (the host never learns what
+ * the list asked for); bytes_uploaded stays 0.
+ *
+ * -1 + errbuf and nothing queued for: a NULL reader ("invalid reader"); a
+ * reader not opened with zsk_reader_open_device ("frame-list read: needs a
+ * device image"); a zstd reader whose census has not been taken ("frame-list
+ * read: zstd is not supported"); a capturing stream ("frame-list read: stream
+ * is capturing"); nidx > 0 with NULL @d_idx ("invalid index list") or NULL
+ * @d_result ("invalid result buffer"); stride == 0 with NULL @d_offsets
+ * ("frame-list read: the packed layout needs d_offsets"); buf_size > 0 and
+ * NULL @d_buf ("invalid buffer"); a @d_buf that is not 16-byte aligned; a
+ * @d_idx, @d_offsets or @d_result that is not 8-byte aligned; the batch
+ * refusals above; on a zstd reader nidx x the census' max_blocks at 2^29
+ * ("frame-list read: the list exceeds the zstd block bound"); a seek table
+ * that reaches past the image ("unexpected EOF").  nidx == 0 returns 0 and
+ * queues only d_result[0] = 0 and, when @d_offsets is given, d_offsets[0] = 0.
+ * A HIP failure after something was queued still queues a fill of d_result[0
+ * .. nidx] with -1 and returns -1.
+ *
+ * Host waits the call may make: growing its buffers (first use, a longer
+ * list), and reusing one of the reader's three batch slots or call tables
+ * while an earlier asynchronous call still runs on it -- taken in turn, as
+ * zsk_preadv_device_async and zsk_preadv_device_indirect take them.
+ * Synchronous reads on the same reader stay correct while such a call is in
+ * flight, and zseek_reader_close waits for it.  Not for a capturing stream;
+ * not for host images.
+ *
+ * A zstd reader.  Accepted once zsk_reader_zstd_census has succeeded on the
+ * reader, whatever zsk_reader_set_zstd_async says.  The batch is decoded by
+ * zsk_zstd_decode_frames_async's machinery.  Its literal scratch is laid out
+ * like the output -- slot i's literals at its destination offset -- so
+ * out_bytes covers the destination span and not the frames' sizes: out_bytes
+ * = min(buf_size, nidx x (stride ? stride : the file's largest dSize)),
+ * max_blocks = nidx x the census' max_blocks, max_sequences = nidx x its
+ * max_sequences, which no nidx entries of the file exceed.  A wide stride
+ * therefore costs literal scratch (and batch size) although the rows are
+ * mostly padding.  The device still checks its own plan against the bounds: an
+ * image rewritten after the census so that a batch exceeds them is refused
+ * whole on the device -- every non-empty slot gets -1, nothing outside the
+ * slots' regions is written, and the next call decodes normally.
+ */
+ZSEEK_EXPORT ssize_t zsk_read_frames_indirect(zseek_reader_t *reader,
+    const int64_t *d_idx, size_t nidx, size_t stride,
+    void *d_buf, size_t buf_size,
+    uint64_t *d_offsets, int64_t *d_result,
+    void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 /*
  * The census of a zstd reader over a device image: one kernel, a lane per

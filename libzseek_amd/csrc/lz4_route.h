@@ -162,6 +162,7 @@ struct Lz4Request {
     uint32_t max_dsize = 0xFFFFFFFFu; // the batch's largest decoded frame, when the caller knows it
     bool in_order = false;            // the caller laid the frames out in order in d_comp
     bool scan_layout = false;         // item slots by the plan's scan whatever the frames' order (not with in_order)
+    bool dsize_bound = false;         // max_dsize is a bound of the frames' sizes, not the largest one's
     bool post = false;                // a HostPost was offered (a lone frame's results straight to the host)
     // a re-plan after a failed reservation: no block route scratch / no
     // scratch for the block-parallel execute's origins
@@ -277,7 +278,9 @@ inline Lz4Plan lz4_plan(const Lz4Request &q, const Lz4Switches &w)
             P.handoff = (q.stages & 8) && (q.max_dsize <= kFrameExecMax || big);
             // a lone frame posts its results to the host itself (no download)
             P.post_here = q.post && P.handoff && n == 1 && !big;
-            P.exec_frames = !(big && n == 1);   // (a lone big frame: nothing for it)
+            // (a lone big frame: nothing for it -- unless max_dsize is only a
+            // bound and the frame may be a small one)
+            P.exec_frames = !(big && n == 1) || q.dsize_bound;
             P.exec_blocks = blocks;
             P.exec_big = big;
             P.big_skip_origin = blocks;

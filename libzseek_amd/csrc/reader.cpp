@@ -1002,6 +1002,8 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
 {
     // per-frame status then fail_at, back to back (one download for both)
     uint32_t *const d_fail = reinterpret_cast<uint32_t *>(s.d_status + a.n);
+    // (a caller's own destination: the frame-list read decodes in place)
+    uint8_t *const d_out = a.out ? a.out : s.d_out;
     hipError_t e = hipSuccess;
     if (a.type == ZSEEK_ZSTD) {
         // (a request's few frames are planned on the host from the pinned
@@ -1009,12 +1011,12 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
         // (the stream-ordered read: no plan on the host and no wait for the
         // device's; the scratch is reserved there from the batch's bounds)
         if (a.zasync) {
-            if (zstd_decode_frames_async(a.d_desc, a.n, a.comp, s.d_out, s.d_status, &s.zs, a.q, *a.zasync, d_fail,
+            if (zstd_decode_frames_async(a.d_desc, a.n, a.comp, d_out, s.d_status, &s.zs, a.q, *a.zasync, d_fail,
                                          a.stop_last, a.max_dsize) != 0)
                 e = hipErrorLaunchFailure;
-        } else if ((a.zplan ? zstd_decode_frames_planned(*a.zplan, a.d_plan, a.d_desc, a.n, a.comp, s.d_out, s.d_status,
+        } else if ((a.zplan ? zstd_decode_frames_planned(*a.zplan, a.d_plan, a.d_desc, a.n, a.comp, d_out, s.d_status,
                                                   &s.zs, a.q, d_fail, a.stop_last)
-                     : zstd_decode_frames(a.d_desc, a.n, a.comp, s.d_out, s.d_status, &s.zs, a.q, d_fail,
+                     : zstd_decode_frames(a.d_desc, a.n, a.comp, d_out, s.d_status, &s.zs, a.q, d_fail,
                                           a.stop_last)) != 0)
             e = hipErrorLaunchFailure;
     } else if (lz4_wave_batch(a.type, a.n)) {
@@ -1024,7 +1026,7 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
         e = hipMemsetD32Async((hipDeviceptr_t)s.d_status, ST_NOT_RUN, a.n, a.q);
         if (e == hipSuccess)
             e = hipMemsetD32Async((hipDeviceptr_t)d_fail, 0, a.n, a.q);
-        if (e == hipSuccess && launch_lz4_wave(a.d_desc, a.n, a.comp, s.d_out, s.d_status, d_fail, a.q) != 0)
+        if (e == hipSuccess && launch_lz4_wave(a.d_desc, a.n, a.comp, d_out, s.d_status, d_fail, a.q) != 0)
             e = hipErrorLaunchFailure;
     } else if (a.h_desc && split_scratch_reserve(&s.split, a.n, split_items_needed(a.h_desc, a.n), a.q) != 0) {
         e = hipErrorOutOfMemory;
@@ -1035,8 +1037,11 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
         rq.max_dsize = a.max_dsize;
         rq.in_order = a.in_order;
         rq.scan_layout = !a.in_order;
+        // (scattered frames come from a device plan: the host knows the
+        // file's largest frame, not which frames the batch holds)
+        rq.dsize_bound = !a.in_order;
         rq.post = a.post != nullptr;
-        if (launch_lz4_split(rq, {a.d_desc, a.comp, s.d_out, s.d_status, d_fail}, a.q, &s.split, a.post, a.posted) != 0)
+        if (launch_lz4_split(rq, {a.d_desc, a.comp, d_out, s.d_status, d_fail}, a.q, &s.split, a.post, a.posted) != 0)
             e = hipErrorLaunchFailure;
     }
     // seek-table checksums (descriptor bit 7) when asked for: XXH64 low 32
@@ -1044,7 +1049,7 @@ hipError_t zsk::decode_batch(Slot &s, const DecodeBatch &a)
     if (e == hipSuccess && a.d_want) {
         if (a.d_want == s.d_ck)
             e = hipMemcpyAsync(s.d_ck, s.h_ck, a.n * sizeof(uint32_t), hipMemcpyHostToDevice, a.q);
-        if (e == hipSuccess && launch_frame_checksums(a.d_desc, a.n, s.d_out, a.d_want, s.d_status, a.q) != 0)
+        if (e == hipSuccess && launch_frame_checksums(a.d_desc, a.n, d_out, a.d_want, s.d_status, a.q) != 0)
             e = hipErrorLaunchFailure;
     }
     return e;

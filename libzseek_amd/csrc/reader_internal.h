@@ -116,7 +116,7 @@ struct PublishStats {
 };
 
 // Queue the decode of one batch -- n frames by the descriptors d_desc, read
-// from comp, into s.d_out, their statuses and fail_at words into s.d_status --
+// from comp, into s.d_out (or `out`), their statuses and fail_at words into s.d_status --
 // on stream q: the wave engine's presets, the decode, the checksum pass.
 struct DecodeBatch {
     zseek_compression_type_t type;
@@ -141,6 +141,9 @@ struct DecodeBatch {
     // the checksum pass: the batch's seek-table words (NULL: no pass; s.d_ck:
     // uploaded here from s.h_ck, behind the decode)
     const uint32_t *d_want = nullptr;
+    // where the descriptors' d_off count from (NULL: the slot's d_out): the
+    // decode launchers' and the checksum pass' output base
+    uint8_t *out = nullptr;
 };
 inline bool lz4_wave_batch(zseek_compression_type_t type, size_t n)   // the batch takes the wave engine
 {

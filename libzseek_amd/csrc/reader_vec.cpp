@@ -4,11 +4,14 @@
 // touch, read run by run and packed back to back; the decode is the
 // contiguous read's (decode_batch), every frame whole (stop_last off); the
 // bytes leave through the gather kernel (range_gather.hip), segment by segment.
+// zsk_read_frames_indirect reads whole frames by index and needs neither
+// staging nor gather: decode_batch writes into the caller's buffer.
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 
+#include "frame_list_plan.h"
 #include "range_plan.h"
 #include "range_plan_dev.h"
 #include "range_result.h"
@@ -694,6 +697,156 @@ extern "C" ZSEEK_EXPORT ssize_t zsk_preadv_device_indirect(zseek_reader_t *r, vo
     else
         g.count_batch();   // (frames_decoded / bytes_decoded: the host never learns them)
     return end_stream_call(ok, &s, c, d_result, nranges, q, err, errbuf);
+}
+
+// zsk_read_frames_indirect (zseek_hip.h): whole frames of a device image by
+// an index list in device memory, each decoded straight into the caller's
+// buffer.  The plan (frame_list_plan.hip) turns slot i's index into a
+// descriptor whose d_off is the slot's own offset of d_buf -- the scan of the
+// sizes before it, or i * stride -- so the decode's output base is d_buf itself:
+// no staging, no gather.  One batch of nidx descriptors (a slot that decodes
+// nothing: padding), sized like the device-planned read's with nidx in place
+// of max_frames; the slot (its statuses and decoder scratch) and the call
+// table (the plan) are taken in turn and left pending.
+extern "C" ZSEEK_EXPORT ssize_t zsk_read_frames_indirect(zseek_reader_t *r, const int64_t *d_idx, size_t nidx,
+                                                         size_t stride, void *d_buf, size_t buf_size,
+                                                         uint64_t *d_offsets, int64_t *d_result, void *stream,
+                                                         char *errbuf)
+{
+    hipStream_t const q = static_cast<hipStream_t>(stream);
+    if (!r) {
+        set_error(errbuf, "invalid reader");
+        return -1;
+    }
+    const DeviceImage *const img = r->img;
+    if (!img) {
+        set_error(errbuf, "frame-list read: needs a device image");
+        return -1;
+    }
+    const bool zstd = r->type == ZSEEK_ZSTD;
+    if (r->type != ZSEEK_LZ4 && !(zstd && img->has_census.load(std::memory_order_acquire))) {
+        set_error(errbuf, "frame-list read: zstd is not supported");
+        return -1;
+    }
+    if (refuse_capturing(q, "frame-list read", errbuf))
+        return -1;
+    if (nidx && !d_idx) {
+        set_error(errbuf, "invalid index list");
+        return -1;
+    }
+    if (nidx && !d_result) {
+        set_error(errbuf, "invalid result buffer");
+        return -1;
+    }
+    if (!stride && !d_offsets) {
+        set_error(errbuf, "frame-list read: the packed layout needs d_offsets");
+        return -1;
+    }
+    if (buf_size && !d_buf) {
+        set_error(errbuf, "invalid buffer");
+        return -1;
+    }
+    // (the decode kernels take any d_off from an aligned base)
+    if ((uintptr_t)d_buf & 15) {
+        set_error(errbuf, "frame-list read: d_buf is not 16-byte aligned");
+        return -1;
+    }
+    if (((uintptr_t)d_offsets | (uintptr_t)d_result | (uintptr_t)d_idx) & 7) {
+        set_error(errbuf, "frame-list read: misaligned list, offsets or result buffer");
+        return -1;
+    }
+    const SeekTable &st = r->st;
+    DeviceGuard keep_device;
+    std::unique_lock<std::shared_mutex> guard(r->lock);
+    PublishStats publish{r};
+    // the decoded span the descriptors can cover: what bounds the parse scratch
+    // and the zstd literal scratch, which is addressed by their d_off
+    const uint64_t unit = stride ? stride : img->max_dsize;
+    if (nidx >= 0x7FFFFFFFull || (unit && nidx > r->batch_bytes / unit)) {
+        set_error(errbuf, "frame-list read: the list exceeds the batch size");
+        return -1;
+    }
+    const uint64_t cover = (uint64_t)nidx * unit;
+    if (cover > 0xFFFFFFFFull) {
+        set_error(errbuf, "frame-list read: the list exceeds 4 GiB");
+        return -1;
+    }
+    // zstd: what any nidx entries of the file need at most, by the census; the
+    // literals of slot i lie at its d_off of the scratch, inside the span the
+    // fitting slots cover
+    ZstdBounds zb{0, 0, 0};
+    if (zstd) {
+        zstd_census_bounds(nidx, img->census.max_blocks, img->census.max_sequences, img->max_dsize, &zb.out_bytes,
+                           &zb.max_blocks, &zb.max_sequences);
+        zb.out_bytes = std::min<uint64_t>(buf_size, cover);
+    }
+    if (nidx && zb.max_blocks >= (1ull << 29)) {
+        set_error(errbuf, "frame-list read: the list exceeds the zstd block bound");
+        return -1;
+    }
+    if (st.c_off.back() > img->size) {
+        set_error(errbuf, "unexpected EOF");
+        return -1;
+    }
+    if (!ensure_lanes(r, errbuf))
+        return -1;
+    DeviceCtx &g = *r->lanes[0];
+    (void)hipSetDevice(g.device);
+    if (nidx == 0) {
+        if (!d_result && !d_offsets)
+            return 0;
+        hipError_t e = d_offsets ? hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), q) : hipSuccess;
+        if (e == hipSuccess && d_result)
+            return answer_no_ranges(d_result, q, errbuf);
+        if (e == hipSuccess)
+            return 0;
+        set_error(errbuf, "GPU decode failed: %s", hipGetErrorString(e));
+        return -1;
+    }
+    const size_t nframes = st.frames();
+    const bool ck = r->verify && st.checksum_flag;
+    const FrameListLayout L = frame_list_layout(nidx, ck);
+    const PlanTables T{img->d_coff, img->d_doff, ck ? img->d_ck : nullptr, nframes, img->bias};
+    const uint32_t M = (uint32_t)nidx;
+    Slot &s = g.take_slot();
+    CallTable &c = g.take_call();
+    char err[ZSEEK_ERRBUF_SIZE] = {0};
+    // (host waits: a slot or table whose earlier asynchronous work has not
+    // finished, and buffers that have to grow)
+    s.drain();
+    // (no staging: 16 bytes stand in as the output base of a call without a buffer)
+    bool ok = c.reserve(0, L.total, err) && s.reserve(0, 16, 0, nidx, false, err);
+    int scratch = 0;
+    if (ok && zstd)
+        scratch = zstd_scratch_reserve(&s.zs, M, zb.out_bytes, zstd_item_capacity(M, zb.max_blocks, zb.max_sequences),
+                                       zb.max_blocks, q);
+    else if (ok && !lz4_wave_batch(r->type, M))
+        scratch = split_scratch_reserve(&s.split, M, (uint64_t)M * slots_of(img->max_csize), q);
+    if (scratch != 0) {
+        set_error(err, "allocate GPU decode buffers failed");
+        ok = false;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        set_error(errbuf, "%s", err);
+        return -1;   // (nothing queued)
+    }
+    // (from here on every return goes through end_stream_call)
+    s.begin_batch(0, 0, 0, 0);
+    ok = launch_frame_list_plan(c.d, L, T, d_idx, nidx, stride, buf_size, d_offsets, d_result, q) == 0;
+    DecodeBatch dec{r->type, q, reinterpret_cast<const FrameDesc *>(c.d + L.desc), M, img->base, img->max_dsize};
+    dec.in_order = false;
+    if (zstd)
+        dec.zasync = &zb;   // (the device checks its plan against them: zstd_fit_kernel)
+    dec.d_want = ck ? reinterpret_cast<const uint32_t *>(c.d + L.ck) : nullptr;
+    dec.out = static_cast<uint8_t *>(d_buf);
+    ok = ok && decode_batch(s, dec) == hipSuccess;
+    ok = ok && launch_frame_list_result(c.d, L, nidx, s.d_status, d_result, q) == 0;
+    if (!ok)
+        set_error(err, "GPU decode failed: %s", hipGetErrorString(hipGetLastError()));
+    else
+        g.count_batch();   // (frames_decoded / bytes_decoded: the host never learns them)
+    return end_stream_call(ok, &s, c, d_result, nidx, q, err, errbuf);
 }
 
 // Vectored reads (zseek_hip.h): many ranges, one decode grid per batch.

@@ -488,6 +488,22 @@ int launch_indirect_plan(uint8_t *d_plan, const PlanLayout &L, const PlanTables 
 int launch_indirect_fix(const uint8_t *d_plan, const PlanLayout &L, uint64_t n, int64_t *d_result,
                         hipStream_t stream);
 
+// The device plan of zsk_read_frames_indirect (frame_list_plan.hip; the
+// arithmetic and the buffer's layout: frame_list_plan.h): from n frame indices
+// in device memory and the resident seek table to n descriptors that decode
+// each slot's frame at its own offset of the caller's buffer (padding for a
+// slot that decodes nothing), the checksum words, d_offsets (NULL allowed in
+// rows mode) and each slot's expected result in d_plan (L.total bytes); it
+// leaves 0 or the span's flag in d_result[n].  launch_frame_list_result goes
+// behind the decode: d_result[i] from the slot's expectation and d_status[i],
+// their count added to d_result[n].  Asynchronous on stream; 0 or -1.
+struct FrameListLayout;
+int launch_frame_list_plan(uint8_t *d_plan, const FrameListLayout &L, const PlanTables &T, const int64_t *d_idx,
+                           uint64_t n, uint64_t stride, uint64_t buf_size, uint64_t *d_offsets, int64_t *d_result,
+                           hipStream_t stream);
+int launch_frame_list_result(const uint8_t *d_plan, const FrameListLayout &L, uint64_t n, const int32_t *d_status,
+                             int64_t *d_result, hipStream_t stream);
+
 // Seek-table checksums (frame_check.hip): frames whose status is ST_OK and
 // whose decoded bytes' XXH64 low 32 bits differ from d_want[f] get
 // ST_SEEK_CHECKSUM.

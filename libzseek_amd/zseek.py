@@ -129,7 +129,7 @@ EXPORTED = [
     "zsk_reader_set_devices", "zsk_reader_devices", "zsk_reader_set_io_threads",
     "zsk_lz4_compress_scratch_size", "zsk_lz4_compress_frames", "zsk_writer_set_gpu_compress",
     "zsk_preadv", "zsk_preadv_device", "zsk_preadv_device_async", "zsk_preadv_device_indirect",
-    "zsk_gather_segments",
+    "zsk_read_frames_indirect", "zsk_gather_segments",
     "zsk_frame_checksums", "zsk_writer_set_checksums", "zsk_write_device",
     "zsk_reader_open_device", "zsk_lz4_image_bound", "zsk_lz4_build_image",
     "zsk_zstd_compress_scratch_size", "zsk_zstd_compress_frames", "zsk_zstd_image_bound", "zsk_zstd_build_image",
@@ -240,6 +240,9 @@ def lib() -> C.CDLL:
     L.zsk_preadv_device_indirect.restype = C.c_ssize_t
     L.zsk_preadv_device_indirect.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_char_p]
+    L.zsk_read_frames_indirect.restype = C.c_ssize_t
+    L.zsk_read_frames_indirect.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
     L.zsk_gather_segments.restype = C.c_int
     L.zsk_gather_segments.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]
@@ -645,6 +648,50 @@ class Reader:
                                                result_ptr, stream, self._err)
         if ret < 0:
             raise ZseekError(self.error)
+
+    def read_frames_indirect(self, idx_ptr: int, nidx: int, dev_ptr: int, buf_size: int, offsets_ptr: int,
+                             result_ptr: int, stride: int = 0, stream: int = 0) -> None:
+        """zsk_read_frames_indirect (a reader from open_device): whole frames
+        by index, the `nidx` int64 indices in device memory at `idx_ptr`, each
+        frame decoded in place into [dev_ptr, dev_ptr + buf_size) and queued on
+        `stream`.  stride 0: packed, slot i at offsets[i] (`offsets_ptr`: nidx
+        + 1 uint64 in device memory, the last the total); stride > 0: slot i at
+        i * stride (`offsets_ptr` may be 0).  `result_ptr`: device memory of
+        nidx + 1 int64 -- each slot's decoded size or -1, then the slots
+        delivered (or PLAN_SPAN).  ZseekError when the call itself fails."""
+        ret = lib().zsk_read_frames_indirect(self._h, idx_ptr or None, nidx, stride, dev_ptr or None, buf_size,
+                                             offsets_ptr or None, result_ptr or None, stream or None, self._err)
+        if ret < 0:
+            raise ZseekError(self.error)
+
+    def read_frames(self, idx, stride: int = 0):
+        """The synchronous convenience over read_frames_indirect: frames `idx`
+        (a sequence or a torch int64 tensor) of a reader from open_device ->
+        (buf, offsets, result) torch tensors on the device.  Packed (stride
+        0): buf is uint8 of the frames' total size, frame i at buf[offsets[i]:
+        offsets[i] + result[i]]; rows: buf is (len(idx), stride).  result[i] is
+        -1 for an index that is no frame and for a frame that failed;
+        result[-1] counts the delivered ones.  Sized from the seek table on the
+        host; waits for the current stream."""
+        import torch
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_idx = torch.as_tensor(idx, dtype=torch.int64).to(dev).contiguous()
+        n = d_idx.numel()
+        _, d_off = self.frames()
+        sizes = np.diff(d_off.astype(np.int64))
+        h_idx = d_idx.cpu().numpy()
+        ok = (h_idx >= 0) & (h_idx < sizes.size)
+        total = n * stride if stride else int(sizes[h_idx[ok]].sum())
+        buf = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)   # (uint64 words: below 2^63)
+        result = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+        q = torch.cuda.current_stream()
+        self.read_frames_indirect(d_idx.data_ptr() if n else 0, n, buf.data_ptr(), total, offsets.data_ptr(),
+                                  result.data_ptr(), stride=stride, stream=q.cuda_stream)
+        q.synchronize()
+        buf = buf[:total]
+        return (buf.view(n, stride) if stride else buf), offsets, result
 
     def stats(self) -> dict:
         s = ReaderStatsC()
