@@ -70,6 +70,13 @@
  *                            compress.c:650-833, planned where the list is).
  *                            zsk_lz4_pieces_bound, zsk_zstd_pieces_bound: their
  *                            capacity, from the piece count alone.
+ *   zsk_lz4_append_image_pieces, zsk_zstd_append_image_pieces — a writer that
+ *                            stays open (zseek_write as data arrives, the table
+ *                            at close, compress.c:650-833) for a file in device
+ *                            memory: new frames behind an image's last frame
+ *                            and a new table over all of them, on the caller's
+ *                            stream.  zsk_lz4_append_bound,
+ *                            zsk_zstd_append_bound: the capacity.
  */
 #ifndef ZSEEK_HIP_H
 #define ZSEEK_HIP_H
@@ -1222,6 +1229,100 @@ ZSEEK_EXPORT int zsk_zstd_build_image_pieces(const void *d_src, size_t src_len,
     const uint32_t *d_sizes, size_t npieces, size_t max_piece, unsigned flags,
     size_t batch_bytes, void *d_image, size_t capacity, int64_t *d_result, void *stream,
     char errbuf[ZSEEK_ERRBUF_SIZE]);
+
+/*
+ * Appending frames to a seekable file that is in device memory: a build from
+ * pieces behind the file's last frame, queued on the caller's stream.
+ *
+ * @d_src, @src_len, @d_sizes, @npieces, @max_piece, @level, @flags,
+ * @batch_bytes, @d_result, @stream: as in zsk_*_build_image_pieces -- the list
+ * is data, an invalid one answers ZSK_IMAGE_BAD_PIECES, the zstd format flags
+ * and the checksum flags mean the same, nothing waits on the host -- except
+ * that @d_sizes is required (a fixed-frame caller passes a list of equal
+ * sizes; "append image: needs a piece list") and @npieces == 0 is valid.
+ * @d_image[0, capacity): holds a seekable file of the same codec, at any byte
+ * alignment.  @d_prev: two int64_t of device memory, 8-byte aligned, read ON
+ * THE STREAM: [0] the existing file's size, [1] its frame count -- the layout
+ * of a builder's d_result, so that an append can be queued directly behind the
+ * build or the append that produced the image, without the host looking.
+ * @d_prev == @d_result is allowed: the words are read before anything of the
+ * call writes them.  @prev_frames: the host's statement of the frame count
+ * (always known to it: every builder takes npieces from the host); it sizes
+ * the scratch that holds the table's entries, 8 or 12 bytes per frame.
+ *
+ * Success, when the stream reaches the end of the call's work:
+ * d_image[0, new size) holds the old frames' bytes untouched, the new frames
+ * packed behind them from the old table's position on, and a seek table over
+ * @prev_frames + @npieces entries; d_result = {new size, prev_frames + npieces,
+ * source bytes consumed}.  Frames are independent and the table is a function
+ * of the frames' sizes, so the file is byte for byte the one that a single
+ * zsk_*_build_image_pieces call over the old pieces followed by the new ones
+ * writes (LZ4: the host writer's file for one zseek_write per piece).
+ * @npieces == 0 rewrites the same table and answers the old size.
+ *
+ * @d_prev and the image are data, not trusted input, and no byte at or past
+ * d_image + capacity is read or written whatever they hold.  The file is
+ * accepted when d_prev[1] == prev_frames; table bytes of prev_frames entries
+ * <= d_prev[0] <= capacity (checked first, before any read of the table); the
+ * table's footer has the seek magic, no reserved descriptor bit, the frame
+ * count prev_frames and a checksum bit equal to @flags & ZSK_IMAGE_CHECKSUMS;
+ * the skippable header's magic and size field match; the entries' compressed
+ * sizes sum to the table's offset; and, when prev_frames > 0, the file starts
+ * with the codec's frame magic (what zseek_reader_open tells the codecs apart
+ * by).  Otherwise d_result[0] = ZSK_IMAGE_BAD_IMAGE and no byte of @d_image is
+ * written.  An accepted file for which zsk_*_append_bound(its size, ...)
+ * exceeds @capacity answers ZSK_IMAGE_NO_ROOM, nothing written either.
+ *
+ * A failure found after the old table was overwritten -- an invalid piece list
+ * in any batch (ZSK_IMAGE_BAD_PIECES), a frame the compressor refused
+ * (ZSK_IMAGE_FAILED) -- ends with the old table written back, so
+ * d_image[0, old size) is again the old file byte for byte; what lies between
+ * that and @capacity is unspecified, and the next call works normally.  When
+ * several apply the answer is, in this order, BAD_IMAGE, NO_ROOM, BAD_PIECES,
+ * FAILED.  A failure code used as the next append's d_prev[0] fails that
+ * call's size check: along a chain queued without looking, every call after a
+ * failed one answers ZSK_IMAGE_BAD_IMAGE and touches nothing.
+ *
+ * zsk_lz4_append_bound / zsk_zstd_append_bound(prev_size, prev_frames, src_len,
+ * npieces, flags): prev_size - table bytes(prev_frames) + the frames' part of
+ * zsk_*_pieces_bound(src_len, npieces) + table bytes(prev_frames + npieces);
+ * 0 when prev_size is below the table bytes of prev_frames.  Monotone in
+ * prev_size: a caller who knows only a bound on the old size allocates by it.
+ *
+ * -1 + errbuf with nothing queued and @d_image untouched, every argument check
+ * before the device is asked for: a capturing stream ("append image: stream is
+ * capturing"); NULL @d_result, @d_prev or @d_sizes; @max_piece 0 or above the
+ * codec's cap; level >= 3; prev_frames + npieces above the seek table's 2^27
+ * frames; @d_result or @d_prev not 8-byte, @d_sizes not 4-byte aligned;
+ * @capacity below zsk_*_append_bound(table bytes(prev_frames), prev_frames,
+ * ...), the smallest file that could be there ("append image: buffer too
+ * small"); no HIP device; a pointer that is not device memory of the image's
+ * device; a fifth builder or append call in progress at once on the device
+ * (the builders' pool).  A HIP failure after something was queued queues a fill
+ * of d_result[0..2] with -1 and returns -1; the old frames' bytes are then
+ * intact and what lies behind them is unspecified.
+ *
+ * A reader's contract is that its image does not change while it is open:
+ * close the readers on an image before appending to it and open a new reader
+ * afterwards.
+ * Left out: removing or replacing frames, selecting frames into a new image,
+ * an image on another device than the source, graph capture, refreshing an
+ * open reader, a fixed-frame mode without a list.
+ */
+#define ZSK_IMAGE_BAD_IMAGE (-3)  /* d_prev / prev_frames do not describe a valid file in d_image */
+#define ZSK_IMAGE_NO_ROOM   (-4)  /* the appended file might not fit capacity */
+ZSEEK_EXPORT size_t zsk_lz4_append_bound(size_t prev_size, size_t prev_frames, size_t src_len,
+    size_t npieces, unsigned flags);
+ZSEEK_EXPORT size_t zsk_zstd_append_bound(size_t prev_size, size_t prev_frames, size_t src_len,
+    size_t npieces, unsigned flags);
+ZSEEK_EXPORT int zsk_lz4_append_image_pieces(const void *d_src, size_t src_len,
+    const uint32_t *d_sizes, size_t npieces, size_t max_piece, int level, unsigned flags,
+    size_t batch_bytes, void *d_image, size_t capacity, const int64_t *d_prev, size_t prev_frames,
+    int64_t *d_result, void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
+ZSEEK_EXPORT int zsk_zstd_append_image_pieces(const void *d_src, size_t src_len,
+    const uint32_t *d_sizes, size_t npieces, size_t max_piece, unsigned flags,
+    size_t batch_bytes, void *d_image, size_t capacity, const int64_t *d_prev, size_t prev_frames,
+    int64_t *d_result, void *stream, char errbuf[ZSEEK_ERRBUF_SIZE]);
 
 #ifdef __cplusplus
 }

@@ -17,4 +17,6 @@ from .zseek import (  # noqa: F401
     zstd_bounds_default, zstd_decode_frames_async, ERR_SCRATCH,
     lz4_pieces_bound, zstd_pieces_bound, lz4_build_image_pieces, zstd_build_image_pieces,
     IMAGE_FAILED, IMAGE_BAD_PIECES,
+    lz4_append_bound, zstd_append_bound, lz4_append_image_pieces, zstd_append_image_pieces,
+    IMAGE_BAD_IMAGE, IMAGE_NO_ROOM,
 )

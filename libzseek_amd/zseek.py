@@ -137,6 +137,7 @@ EXPORTED = [
     "zsk_zstd_bounds_default", "zsk_zstd_decode_frames_async", "zsk_reader_set_zstd_async",
     "zsk_reader_zstd_census",
     "zsk_lz4_pieces_bound", "zsk_zstd_pieces_bound", "zsk_lz4_build_image_pieces", "zsk_zstd_build_image_pieces",
+    "zsk_lz4_append_bound", "zsk_zstd_append_bound", "zsk_lz4_append_image_pieces", "zsk_zstd_append_image_pieces",
 ]
 
 _lib = None
@@ -285,6 +286,17 @@ def lib() -> C.CDLL:
     L.zsk_zstd_build_image_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_char_p]
+    for fn in (L.zsk_lz4_append_bound, L.zsk_zstd_append_bound):
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint]
+    L.zsk_lz4_append_image_pieces.restype = C.c_int
+    L.zsk_lz4_append_image_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
+                                              C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_char_p]
+    L.zsk_zstd_append_image_pieces.restype = C.c_int
+    L.zsk_zstd_append_image_pieces.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                               C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.c_void_p, C.c_char_p]
     _lib = L
     return L
 
@@ -1196,6 +1208,60 @@ def zstd_build_image_pieces(src, sizes, max_piece: int, image, result, checksums
     err = C.create_string_buffer(ERRBUF)
     if lib().zsk_zstd_build_image_pieces(s, n, z, k, max_piece, _image_flags(checksums, content_checksums, full, wide),
                                          batch_bytes, im, cap, res, q, err) != 0:
+        raise ZseekError(err.value.decode())
+
+
+IMAGE_BAD_IMAGE = -3    # ZSK_IMAGE_BAD_IMAGE
+IMAGE_NO_ROOM = -4      # ZSK_IMAGE_NO_ROOM
+
+
+def lz4_append_bound(prev_size: int, prev_frames: int, src_len: int, npieces: int, checksums: bool = False) -> int:
+    """zsk_lz4_append_bound: the capacity zsk_lz4_append_image_pieces asks for
+    on a file of prev_size bytes and prev_frames frames (0: prev_size cannot
+    hold such a table)."""
+    return int(lib().zsk_lz4_append_bound(prev_size, prev_frames, src_len, npieces,
+                                          IMAGE_CHECKSUMS if checksums else 0))
+
+
+def zstd_append_bound(prev_size: int, prev_frames: int, src_len: int, npieces: int, checksums: bool = False) -> int:
+    """zsk_zstd_append_bound, as lz4_append_bound."""
+    return int(lib().zsk_zstd_append_bound(prev_size, prev_frames, src_len, npieces,
+                                           IMAGE_CHECKSUMS if checksums else 0))
+
+
+def lz4_append_image_pieces(src, sizes, max_piece: int, image, prev, prev_frames: int, result, level: int = 0,
+                            checksums: bool = False, batch_bytes: int = 0, stream: int | None = None,
+                            src_len: int | None = None, npieces: int | None = None,
+                            capacity: int | None = None) -> None:
+    """zsk_lz4_append_image_pieces: queue, on `stream` (default: torch's
+    current stream), one frame per piece of `sizes` from `src` behind the last
+    frame of the seekable LZ4 file that `image` holds, and a seek table over
+    all frames.  `prev`: two int64 of device memory, the file's size and frame
+    count (a builder's `result`; it may be `result` itself); `prev_frames`: the
+    frame count as the host knows it.  The answer lands in `result` (the new
+    size or IMAGE_FAILED / IMAGE_BAD_PIECES / IMAGE_BAD_IMAGE / IMAGE_NO_ROOM,
+    the frames, the source bytes used).  No host wait.  Arguments otherwise as
+    lz4_build_image_pieces; `sizes` is required."""
+    s, n, z, k, im, cap, res, q = _pieces_args(src, sizes, max_piece, image, result, stream, src_len, npieces, capacity)
+    err = C.create_string_buffer(ERRBUF)
+    pv = prev if prev is None or isinstance(prev, int) else prev.data_ptr()
+    if lib().zsk_lz4_append_image_pieces(s, n, z, k, max_piece, level, IMAGE_CHECKSUMS if checksums else 0,
+                                         batch_bytes, im, cap, pv, prev_frames, res, q, err) != 0:
+        raise ZseekError(err.value.decode())
+
+
+def zstd_append_image_pieces(src, sizes, max_piece: int, image, prev, prev_frames: int, result,
+                             checksums: bool = False, content_checksums: bool = False, full: bool = False,
+                             wide: bool = False, batch_bytes: int = 0, stream: int | None = None,
+                             src_len: int | None = None, npieces: int | None = None,
+                             capacity: int | None = None) -> None:
+    """zsk_zstd_append_image_pieces, as lz4_append_image_pieces; the flags are
+    zstd_build_image's."""
+    s, n, z, k, im, cap, res, q = _pieces_args(src, sizes, max_piece, image, result, stream, src_len, npieces, capacity)
+    err = C.create_string_buffer(ERRBUF)
+    pv = prev if prev is None or isinstance(prev, int) else prev.data_ptr()
+    if lib().zsk_zstd_append_image_pieces(s, n, z, k, max_piece, _image_flags(checksums, content_checksums, full, wide),
+                                          batch_bytes, im, cap, pv, prev_frames, res, q, err) != 0:
         raise ZseekError(err.value.decode())
 
 
